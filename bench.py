@@ -23,6 +23,14 @@ When started without torchrun and ``--gpus N > 1`` the parent spawns N child
 processes (one per GPU, RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* in their env)
 BEFORE anything touches the GPU, waits for them and exits with their status.
 
+A plain run sets up, warms up, times the K steps and prints one JSON line.
+``--full`` adds what the headline figure does not need: at N > 1 one extra
+step with per-collective timing (the ``comm_diag`` table), and the N = 1 step
+time left behind for later N > 1 runs to compare themselves with.
+``--dump-outputs DIR`` writes what the last timed step returned and left behind
+(loss, gradient norm, a fixed seeded sample of the updated parameters) as
+``DIR/<name>.npy``; the same arguments give the same inputs in every run.
+
 Other BASELINE configs, one command each (need >= tp*pp GPUs):
     --preset llama7b-tp8-seq4096     Llama-2-7B, TP=8 (SP), seq 4096
     --preset falcon40b-tp4-pp2       Falcon-40B, TP=4 x PP=2 interleaved, 8 micro-batches
@@ -107,9 +115,17 @@ def _parse(argv=None):
     ap.add_argument("--vpp_layers", type=int, default=None,
                     help="layers per virtual pipeline stage (interleaved 1F1B)")
     ap.add_argument("--recompute", default=None, choices=["selective", "full"])
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the per-collective table of "
+                         "one extra step at --gpus > 1 and the N=1 step-time reference that "
+                         "multi-GPU records compare themselves with")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one returned and left "
+                         "behind (loss, gradient norm, a fixed sample of the updated "
+                         "parameters) as DIR/<name>.npy")
     ap.add_argument("--comm_diag", action="store_true",
                     help="add the per-collective table of one extra timed-collective step "
-                         "(always on at --gpus > 1)")
+                         "(on with --full at --gpus > 1)")
     ap.add_argument("--recompute_budget_gb", type=float, default=None,
                     help="recompute only what the memory model needs to fit this peak")
     ap.add_argument("--no_sp", action="store_true")
@@ -309,6 +325,44 @@ def _n1_ref_path(label, par):
     return os.path.join(tempfile.gettempdir(), f"ema_bench_n1_{key}.json")
 
 
+DUMP_PARAM_SAMPLE = 4 * 2**20  # sampled parameter elements (16 MiB of float32)
+
+
+def _dump_outputs(path, grad_norm, losses, chunks):
+    """Write what the last timed ``train_step`` handed back and left behind as
+    ``path/<name>.npy``: its loss (``lm_loss``) and gradient norm, the loss of
+    every step so far (``losses``: one float per step, already shipped from the
+    last pipeline stage), and a fixed sample of rank 0's updated parameters
+    (its shard under TP / PP).  The sample uses the same seeded indices for the
+    same model, drawn with replacement and spread over the parameters in
+    proportion to their size with at least one element each (so a little more
+    than ``DUMP_PARAM_SAMPLE`` elements), so two builds run with the same
+    arguments compare output for output."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+
+    def f64(v):
+        return np.asarray(float("nan") if v is None else float(v), dtype=np.float64).reshape(1)
+
+    np.save(os.path.join(path, "lm_loss.npy"), f64(losses[-1] if losses else None))
+    np.save(os.path.join(path, "grad_norm.npy"), f64(grad_norm))
+    np.save(os.path.join(path, "loss_per_step.npy"), np.asarray(losses, dtype=np.float64))
+    params = [p for m in chunks for _, p in sorted(m.named_parameters(), key=lambda kv: kv[0])]
+    total = sum(p.numel() for p in params)
+    gen = torch.Generator().manual_seed(1234)
+    parts = []
+    with torch.no_grad():
+        for p in params:
+            flat = p.detach().reshape(-1)
+            n = min(flat.numel(), max(1, DUMP_PARAM_SAMPLE * flat.numel() // max(total, 1)))
+            if n < flat.numel():
+                idx = torch.randint(flat.numel(), (n,), generator=gen).to(flat.device)
+                flat = flat[idx]
+            parts.append(flat.float().cpu())
+    np.save(os.path.join(path, "params_sample.npy"), torch.cat(parts).numpy())
+
+
 def _label(cfg, shape, a):
     names = {"llama2-7b": "Llama-2-7B", "llama2-13b": "Llama-2-13B", "llama2-70b": "Llama-2-70B",
              "falcon-7b": "Falcon-7B", "falcon-40b": "Falcon-40B"}
@@ -392,13 +446,14 @@ def main(argv=None):
     comm.report(reset=True)
     if on_gpu:
         torch.cuda.reset_peak_memory_stats()
+    last = None
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        step()
+        last = step()
     sync()
     dt = time.perf_counter() - t0
     comm_rep = comm.report(reset=True)
-    dev = torch.device("cuda", torch.cuda.current_device()) if on_gpu else torch.device("cpu")
+    dev =torch.device("cuda", torch.cuda.current_device()) if on_gpu else torch.device("cpu")
     t = torch.tensor([dt], dtype=torch.float64, device=dev)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)  # slowest rank defines the step time
     dt = float(t.item())
@@ -412,8 +467,21 @@ def main(argv=None):
     if state.get_pipeline_model_parallel_world_size() > 1:
         src = state.get_pipeline_model_parallel_last_rank()
         dist.broadcast(loss_t, src=src, group=state.get_pipeline_model_parallel_group())
+    if a.dump_outputs and last is not None:
+        for m in chunks:  # the dist-opt parameter all-gather still in flight
+            if hasattr(m, "wait_param_sync"):
+                m.wait_param_sync()
+        # every step's loss, shipped from the last pipeline stage like loss_t
+        n_done = a.warmup + a.steps
+        all_t = torch.tensor([float(l) for l in losses] if len(losses) == n_done
+                             else [float("nan")] * n_done, dtype=torch.float64, device=dev)
+        if state.get_pipeline_model_parallel_world_size() > 1:
+            dist.broadcast(all_t, src=state.get_pipeline_model_parallel_last_rank(),
+                           group=state.get_pipeline_model_parallel_group())
+        if dist.get_rank() == 0:
+            _dump_outputs(a.dump_outputs, last[2], all_t.tolist(), chunks)
     diag = None
-    if world > 1 or a.comm_diag:
+    if (world > 1 and a.full) or a.comm_diag:
         # one more step, untimed, with per-collective HIP-event timing
         comm.set_timing(True)
         t1 = time.perf_counter()
@@ -506,10 +574,11 @@ def main(argv=None):
             rec.update(_proxy_comm(comm_rep, par["sim_tp"], a.steps, 1000.0 * dt / a.steps,
                                    a.xgmi_busbw_gbs))
         # weak-scaling reference: an N=1 run of the same per-GPU config leaves its
-        # step time behind; an N>1 run reports the step time it lost to N ranks
+        # step time behind (with --full); an N>1 run with the per-collective table
+        # reports the step time it lost to N ranks
         if not a.proxy and par["dp"] >= 1:
             ref_path = _n1_ref_path(label, par)
-            if world == 1 and on_gpu:
+            if world == 1 and on_gpu and a.full:
                 try:
                     with open(ref_path, "w") as f:
                         json.dump({"ms_per_step": rec["ms_per_step"]}, f)

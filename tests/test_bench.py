@@ -5,6 +5,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -21,7 +23,7 @@ def _run(args, timeout=600):
 
 
 def test_bench_spawns_ranks():
-    rec = _run(["--gpus", "4", "--steps", "1", "--warmup", "1"])
+    rec = _run(["--gpus", "4", "--steps", "1", "--warmup", "1", "--full"])
     assert rec["n_gpus"] == 4
     assert rec["config"]["parallelism"] == "dp4+distopt"
     assert rec["config"]["global_batch"] == 4 * rec["config"]["micro_batch"] * \
@@ -45,6 +47,30 @@ def test_bench_spawns_ranks():
 def test_bench_single_rank_default():
     rec = _run(["--steps", "2", "--warmup", "1"])
     assert rec["n_gpus"] == 1 and rec["config"]["parallelism"] == "dp1"
+
+
+def test_bench_plain_run_is_lean_and_dumps_repeatable_outputs(tmp_path):
+    """A plain multi-rank run carries no ``comm_diag`` (that extra step is behind
+    ``--full``); ``--dump-outputs`` writes the last timed step's loss, gradient
+    norm and parameter sample as float .npy files, identical from run to run.
+    Two pipeline stages: rank 0 writes the files, the loss lives on rank 1."""
+    import numpy as np
+    recs = [_run(["--gpus", "2", "--pp", "2", "--steps", "2", "--warmup", "1", "--dump-outputs",
+                  str(tmp_path / d)]) for d in ("a", "b")]
+    assert "comm_diag" not in recs[0] and recs[0]["steps"] == 2 and recs[0]["pp"] == 2
+    assert recs[0]["ms_per_step"] > 0
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["grad_norm.npy", "lm_loss.npy", "loss_per_step.npy", "params_sample.npy"]
+    size = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and np.isfinite(x).all(), n
+        np.testing.assert_array_equal(x, y, err_msg=n)
+        size += x.nbytes
+    assert 0 < size <= 64 * 2**20
+    assert np.load(tmp_path / "a" / "loss_per_step.npy").shape == (3,)
+    assert float(np.load(tmp_path / "a" / "lm_loss.npy")[0]) == pytest.approx(
+        recs[0]["final_loss"], abs=1e-4)
 
 
 def test_bench_rank_failure_propagates():
@@ -81,9 +107,6 @@ def test_readme_headline_quotes_driver_record():
     rec = json.load(open(os.path.join(ROOT, m.group(2))))
     value = rec["parsed"]["value"] if "parsed" in rec else rec["value"]
     assert abs(float(m.group(1)) - value / 1000) < 0.051, (m.group(1), value)
-
-
-import pytest  # noqa: E402
 
 
 @pytest.mark.parametrize("preset,parallel,groups", [

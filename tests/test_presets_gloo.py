@@ -19,7 +19,7 @@ def _bench8(preset):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8",
-                          "--steps", "1", "--warmup", "1", "--preset", preset],
+                          "--steps", "1", "--warmup", "1", "--full", "--preset", preset],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
