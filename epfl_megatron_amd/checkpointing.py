@@ -359,8 +359,12 @@ def load_args_from_checkpoint(args, load_arg="load"):
     for n in ("num_layers", "hidden_size", "ffn_hidden_size", "seq_length",
               "num_attention_heads", "num_attention_heads_kv", "kv_channels",
               "max_position_embeddings", "glu_activation", "layernorm_epsilon",
-              "rope_scaling_factor"):
+              "rope_scaling_factor", "rope_theta", "sliding_window_size"):
         _set(n)
+    # --rope_theta has a non-None default, so "not given" is "still the default":
+    # a checkpoint that carries another base (Code Llama, Mistral: 1e6) wins then
+    if getattr(args, "rope_theta", None) == 10000.0:
+        _set("rope_theta", force=True)
     for n in ("position_embedding_type", "parallel_attn", "parallel_layernorm", "use_rms_norm",
               "tie_embed_logits", "make_vocab_size_divisible_by", "use_bias",
               "padded_vocab_size"):

@@ -76,6 +76,11 @@ FLAG_TABLE = {
               default=PositionEmbeddingType.absolute,
               choices=list(PositionEmbeddingType)),
         _flag("--rope_scaling_factor", type=float, default=1.0),
+        _flag("--rope_theta", type=float, default=10000.0,
+              help="RoPE base (Code Llama, Mistral v0.2+: 1e6)"),
+        _flag("--sliding_window_size", type=int, default=None,
+              help="sliding-window attention: each query sees the last W keys only "
+                   "(Mistral-7B-v0.1: 4096)"),
         _flag("--parallel_attn", action="store_true"),
         _flag("--parallel_layernorm", action="store_true"),
         _flag("--no_tie_embed_logits", action="store_false", dest="tie_embed_logits"),
@@ -539,6 +544,17 @@ def _derive_schedule_and_model(args):
         _require(args.max_position_embeddings >= args.decoder_seq_length,
                  "max_position_embeddings must be >= decoder_seq_length")
     _require(args.rope_scaling_factor >= 1, "rope_scaling_factor must be >= 1")
+    if getattr(args, "rope_theta", None) is None:
+        args.rope_theta = 10000.0
+    _require(args.rope_theta > 0, "rope_theta must be positive")
+    window = getattr(args, "sliding_window_size", None)
+    if window is not None:
+        _require(window >= 1, "sliding_window_size must be >= 1")
+        _require((getattr(args, "context_parallel_size", 1) or 1) == 1,
+                 "sliding-window attention is not available with --context_parallel_size > 1")
+        _require(getattr(args, "model_name", None) in (None,) + _CAUSAL_MODEL_NAMES
+                 and args.decoder_seq_length is None,
+                 "sliding-window attention needs a causal decoder-only model")
     if args.lr is not None:
         _require(args.min_lr <= args.lr, "min_lr must be <= lr")
     if args.save is not None:
@@ -556,6 +572,10 @@ def _derive_schedule_and_model(args):
     else:
         _require(args.start_weight_decay is not None and args.end_weight_decay is not None,
                  "non-constant weight decay needs start and end values")
+
+
+# --model_name values whose attention is causal self-attention only
+_CAUSAL_MODEL_NAMES = ("gpt", "llama", "llama2", "codellama", "falcon", "mistral")
 
 
 def _derive_recompute_and_parallel_features(args):

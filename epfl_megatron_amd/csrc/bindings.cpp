@@ -563,6 +563,14 @@ static void set_docs(ema::AttnParams& p, const c10::optional<at::Tensor>& docs) 
   p.doc_end = p.doc_start + (int64_t)p.b * p.sq;
 }
 
+// Sliding window (see AttnParams; call after coff is final): a window that
+// reaches past every row's first key is no window.
+static void set_window(ema::AttnParams& p, int64_t window) {
+  TORCH_CHECK(window >= 0, "sliding window must be >= 0 (0: none)");
+  TORCH_CHECK(window == 0 || p.causal, "a sliding window needs causal attention");
+  p.window = window >= (int64_t)p.sq + p.coff ? 0 : (int)window;
+}
+
 void flash_attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, at::Tensor out,
                     at::Tensor lse, int64_t b, int64_t sq, int64_t sk, int64_t nq, int64_t nkv,
                     int64_t hd, std::vector<int64_t> qs, std::vector<int64_t> ks,
@@ -570,11 +578,12 @@ void flash_attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& 
                     const c10::optional<at::Tensor>& rope_cos,
                     const c10::optional<at::Tensor>& rope_sin,
                     const c10::optional<at::Tensor>& rope_pos,
-                    const c10::optional<at::Tensor>& docs) {
+                    const c10::optional<at::Tensor>& docs, int64_t window) {
   check_gpu(q, "q");
   auto p = make_attn(q, k, v, out, lse, b, sq, sk, nq, nkv, hd, qs, ks, vs, os, causal, scale);
   set_rope(p, rope_cos, rope_sin, rope_pos);
   set_docs(p, docs);
+  set_window(p, window);
   ema::flash_attn_fwd(p, dtype_code(q), cur_stream());
 }
 
@@ -587,7 +596,7 @@ void flash_attn_fwd_merge(const at::Tensor& q, const at::Tensor& k, const at::Te
                           int64_t nq, int64_t nkv, int64_t hd, std::vector<int64_t> qs,
                           std::vector<int64_t> ks, std::vector<int64_t> vs, bool causal,
                           double scale, bool merge, const c10::optional<at::Tensor>& docs,
-                          int64_t coff) {
+                          int64_t coff, int64_t window) {
   check_gpu(q, "q");
   TORCH_CHECK(o32.scalar_type() == at::kFloat && o32.dim() == 4 && o32.size(0) == b &&
                   o32.size(1) == sq && o32.size(2) == nq && o32.size(3) == hd && o32.stride(3) == 1 &&
@@ -619,6 +628,7 @@ void flash_attn_fwd_merge(const at::Tensor& q, const at::Tensor& k, const at::Te
     TORCH_CHECK(causal && coff >= sk - sq, "flash_attn_fwd_merge: coff needs the causal kernel");
     p.coff = (int)coff;
   }
+  set_window(p, window);
   ema::flash_attn_fwd(p, dtype_code(q), cur_stream());
 }
 
@@ -630,7 +640,7 @@ void flash_attn_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tenso
                     const c10::optional<at::Tensor>& rope_cos,
                     const c10::optional<at::Tensor>& rope_sin,
                     const c10::optional<at::Tensor>& rope_pos,
-                    const c10::optional<at::Tensor>& docs, int64_t coff) {
+                    const c10::optional<at::Tensor>& docs, int64_t coff, int64_t window) {
   check_gpu(q, "q");
   auto f = make_attn(q, k, v, out, lse, b, sq, sk, nq, nkv, hd, qs, ks, vs, os, causal, scale);
   set_rope(f, rope_cos, rope_sin, rope_pos);
@@ -639,6 +649,7 @@ void flash_attn_bwd(const at::Tensor& dout, const at::Tensor& q, const at::Tenso
     TORCH_CHECK(causal && coff >= sk - sq, "flash_attn_bwd: coff needs the causal kernel");
     f.coff = (int)coff;
   }
+  set_window(f, window);
   TORCH_CHECK(dout.scalar_type() == q.scalar_type(), "dout dtype mismatch");
   TORCH_CHECK(dout.stride(-1) == 1, "dout head_dim must be contiguous");
   ema::AttnBwdParams p{};
@@ -822,8 +833,9 @@ void flash_decode(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                   int64_t b, int64_t sk, int64_t nq, int64_t nkv, int64_t hd,
                   std::vector<int64_t> qs, std::vector<int64_t> ks, std::vector<int64_t> vs,
                   std::vector<int64_t> os, double scale, const c10::optional<at::Tensor>& kv_len,
-                  int64_t kpw) {
+                  int64_t kpw, int64_t window) {
   check_gpu(q, "q");
+  TORCH_CHECK(window >= 0, "sliding window must be >= 0 (0: none)");
   if (kv_len) {
     TORCH_CHECK(kv_len->is_cuda() && kv_len->scalar_type() == at::kInt && kv_len->numel() >= 1,
                 "kv_len must be a device int32 tensor");
@@ -860,6 +872,7 @@ void flash_decode(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
   if (kpw <= 0) kpw = ema::flash_decode_kpw((int)b, (int)sk, (int)nq, (int)nkv);
   TORCH_CHECK(kpw == 8 || kpw == 16 || kpw == 64, "decode attention: kpw must be 8, 16 or 64");
   p.kpw = (int)kpw;
+  p.window = window >= sk ? 0 : (int)window;  // sk bounds the valid keys
   const int64_t ns = ema::flash_decode_splits((int)sk, (int)kpw);
   auto ws = at::empty({b * nq * ns * (hd + 2)}, q.options().dtype(at::kFloat));
   p.ws_o = ws.data_ptr<float>();
@@ -1261,18 +1274,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("opt_prep", &opt_prep);
   m.def("bias_dropout_add_fwd", &bias_dropout_add_fwd);
   m.def("bias_dropout_add_bwd", &bias_dropout_add_bwd);
-  m.def("flash_attn_fwd", &flash_attn_fwd);
+  m.def("flash_attn_fwd", &flash_attn_fwd, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"),
+        py::arg("lse"), py::arg("b"), py::arg("sq"), py::arg("sk"), py::arg("nq"), py::arg("nkv"),
+        py::arg("hd"), py::arg("qs"), py::arg("ks"), py::arg("vs"), py::arg("os"),
+        py::arg("causal"), py::arg("scale"), py::arg("rope_cos"), py::arg("rope_sin"),
+        py::arg("rope_pos"), py::arg("docs"), py::arg("window") = 0);
   m.def("flash_attn_fwd_merge", &flash_attn_fwd_merge, py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("o32"), py::arg("lse"), py::arg("b"), py::arg("sq"), py::arg("sk"), py::arg("nq"),
         py::arg("nkv"), py::arg("hd"), py::arg("qs"), py::arg("ks"), py::arg("vs"),
         py::arg("causal"), py::arg("scale"), py::arg("merge"), py::arg("docs") = py::none(),
-        py::arg("coff") = -1);
+        py::arg("coff") = -1, py::arg("window") = 0);
   m.def("flash_attn_bwd", &flash_attn_bwd, py::arg("dout"), py::arg("q"), py::arg("k"),
         py::arg("v"), py::arg("out"), py::arg("lse"), py::arg("dq"), py::arg("dk"), py::arg("dv"),
         py::arg("b"), py::arg("sq"), py::arg("sk"), py::arg("nq"), py::arg("nkv"), py::arg("hd"),
         py::arg("qs"), py::arg("ks"), py::arg("vs"), py::arg("os"), py::arg("causal"),
         py::arg("scale"), py::arg("rope_cos"), py::arg("rope_sin"), py::arg("rope_pos"),
-        py::arg("docs"), py::arg("coff") = -1);
+        py::arg("docs"), py::arg("coff") = -1, py::arg("window") = 0);
   m.def("fa_set_stamps", &fa_set_stamps);
   m.def("fa_set_pairing", &ema::fa_set_pairing);
   m.def("fa_set_kv2", &ema::fa_set_kv2);
@@ -1296,7 +1313,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_decode", &flash_decode, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"),
         py::arg("b"), py::arg("sk"), py::arg("nq"), py::arg("nkv"), py::arg("hd"), py::arg("qs"),
         py::arg("ks"), py::arg("vs"), py::arg("os"), py::arg("scale"), py::arg("kv_len"),
-        py::arg("kpw") = 0);
+        py::arg("kpw") = 0, py::arg("window") = 0);
   m.def("skinny_gemm", &skinny_gemm, py::arg("x"), py::arg("w"), py::arg("packed") = false);
   m.def("skinny_gemm_supported", &skinny_gemm_supported);
   m.def("skinny_norm_gemm", &skinny_norm_gemm, py::arg("x"), py::arg("w"), py::arg("norm_w"),

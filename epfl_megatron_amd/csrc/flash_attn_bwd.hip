@@ -24,6 +24,11 @@
 // each key block's query range at its last key's document end and masks
 // queries whose document starts after the key (doc starts streamed with LSE).
 //
+// Sliding window (optional, p.window > 0): the lower key bound of a row becomes
+// max(document start, row + coff - window + 1), computed in registers; the
+// dK/dV kernel also ends a key block at the last query whose window holds its
+// last key.
+//
 // RoPE (optional, p.rope_cos != nullptr): the forward rotated Q and K, so dQ
 // and dK come out in the rotated basis; both kernels apply R^T to them in
 // their epilogue (fp32, before the bf16 store), replacing a separate
@@ -97,6 +102,10 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkdv2_k(const AttnBwdParams P) 
   const float sl2 = p.scale * 1.4426950408889634f;
   const int ngs = p.nkv * S;
   const int nitems = ((p.sk + BNK - 1) / BNK) * ngs * p.b;
+  // sliding window: key k is visible to query q iff q < k + wq (no window: a
+  // bound no row reaches).  It only tightens the row bound sq of a key, so the
+  // step loop tests the per-item bounds sq_w / rowlim where it tested sq.
+  const int wq = CAUSAL && p.window > 0 ? p.window - off : 1 << 29;
 
   // item -> key block (heaviest first), KV group, query-head split, batch
   struct Item {
@@ -120,6 +129,10 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkdv2_k(const AttnBwdParams P) 
     if (CAUSAL && p.doc_end) {  // no query past the last key's document sees this block
       const int kl = I.nb * BNK + BNK - 1 < p.sk ? I.nb * BNK + BNK - 1 : p.sk - 1;
       q_end = p.doc_end[(int64_t)I.b * p.sq + kl];
+    }
+    if (CAUSAL) {  // nor does a query whose window starts past the last key
+      const int kl = I.nb * BNK + BNK - 1 < p.sk ? I.nb * BNK + BNK - 1 : p.sk - 1;
+      q_end = min(q_end, max(kl + wq, 0));
     }
     I.nsteps_q = q_end > qf ? (q_end - qf + BQ2 - 1) / BQ2 : 0;
     I.nsteps = r_per * I.nsteps_q;
@@ -221,6 +234,9 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkdv2_k(const AttnBwdParams P) 
   while (true) {
     const int kbase = cur.nb * BNK + wave * 32;
     const int key = kbase + c;
+    // first row that the wave's first key does not see; end of the rows this lane's key sees
+    const int sq_w = CAUSAL ? min(p.sq, kbase + wq) : p.sq;
+    const int rowlim = CAUSAL ? min(p.sq, key + wq) : p.sq;
     x8 kf[KS], vf[KS];
 #pragma unroll
     for (int kk = 0; kk < KS; ++kk) {
@@ -298,7 +314,7 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkdv2_k(const AttnBwdParams P) 
         });
         mfma_drain();
         const bool docs = CAUSAL && p.doc_start;
-        const bool need_mask = (q0s + 32 > p.sq) || (kbase + 32 > p.sk) ||
+        const bool need_mask = (q0s + 32 > sq_w) || (kbase + 32 > p.sk) ||
                                (CAUSAL && (kbase + 31 > q0s + off)) || docs;
         // P = exp2(S scale log2e - lse log2e), the argument by packed fma
         const f2 sc2 = {sl2, sl2};
@@ -319,13 +335,13 @@ __global__ __launch_bounds__(256, 1) void fa_bwd_dkdv2_k(const AttnBwdParams P) 
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
               const int qr = q0s + acc_row(i, h);
-              const bool ok = (qr < p.sq) & (key < p.sk) & (key <= qr + off) &
+              const bool ok = (qr < rowlim) & (key < p.sk) & (key <= qr + off) &
                               (key >= ds4[i >> 2][i & 3]);
               sacc[i] = ok ? sacc[i] : 0.f;
             }
           } else {
             // row rc = acc_row(i, 0) of the block is kept iff lo <= rc <= hi
-            int hi = p.sq - 1 - q0s - 4 * h;
+            int hi = rowlim - 1 - q0s - 4 * h;
             if (key >= p.sk) hi = -1;
             const int lo = CAUSAL ? key - off - q0s - 4 * h : -(1 << 30);
 #pragma unroll
@@ -511,16 +527,30 @@ __global__ __launch_bounds__(WAVES * 64, 8 / WAVES) void fa_bwd_dq2_k(const Attn
     const int wt = wl > 0 ? (wl + KT - 1) / KT : 0;
     wtiles = wt < ntiles ? wt : ntiles;
   }
-  // document mask (as in the forward): start at the first row's document
+  // lower key bound (document mask and / or sliding window, as in the forward):
+  // start at the first row's bound
+  const bool lob = CAUSAL && (p.doc_start || p.window > 0);
   int t0 = 0, wt0 = 0, ds_row = 0, ds_wmax = 0;
-  if (CAUSAL && p.doc_start) {
-    const int* D = p.doc_start + (int64_t)b * p.sq;
+  if (lob) {
     const int r0 = qb * BMW < p.sq ? qb * BMW : p.sq - 1;
     const int w0 = q0w < p.sq ? q0w : p.sq - 1, w1 = q0w + 31 < p.sq ? q0w + 31 : p.sq - 1;
-    t0 = D[r0] / KT;
-    wt0 = D[w0] / KT;
-    ds_wmax = D[w1];
-    ds_row = D[qrow_c];
+    int l0 = 0, lw0 = 0;
+    if (p.doc_start) {
+      const int* D = p.doc_start + (int64_t)b * p.sq;
+      l0 = D[r0];
+      lw0 = D[w0];
+      ds_wmax = D[w1];
+      ds_row = D[qrow_c];
+    }
+    if (p.window > 0) {
+      const int wo = off - p.window + 1;  // row + wo: the row's first visible key
+      l0 = max(l0, r0 + wo);
+      lw0 = max(lw0, w0 + wo);
+      ds_wmax = max(ds_wmax, w1 + wo);
+      ds_row = max(ds_row, qrow_c + wo);
+    }
+    t0 = l0 / KT;
+    wt0 = lw0 / KT;
   }
 
   // K / V tiles arrive by LDS-DMA (global_load_lds_dwordx4: lane-linear LDS
@@ -669,7 +699,7 @@ __global__ __launch_bounds__(WAVES * 64, 8 / WAVES) void fa_bwd_dq2_k(const Attn
           int hi = p.sk - 1 - kb - 4 * h;
           if (CAUSAL) hi = min(hi, qrow + off - kb - 4 * h);
           if (qrow >= p.sq) hi = -1;
-          if (CAUSAL && p.doc_start) {
+          if (lob) {
             const int lo = ds_row - kb - 4 * h;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {

@@ -28,6 +28,10 @@
 // at the key tile of its first row's document; keys before a row's document
 // start are masked like the causal upper triangle.
 //
+// Sliding window (p.window > 0): the same lower bound, row + coff - window + 1
+// (max with the document start), computed in registers; a block visits only
+// the key tiles its rows' windows touch.
+//
 // Fused RoPE (p.rope_cos set): Q is rotated in registers right after its load
 // and written back in place (only this workgroup reads those rows), so the
 // backward sees rotated Q; K is rotated by a k-only pre-pass (rope.hip).
@@ -102,17 +106,31 @@ __global__ __launch_bounds__(WAVES * 64, 8 / WAVES) void fa_fwd_k(const AttnPara
     const int wt = wl > 0 ? (wl + KT - 1) / KT : 0;
     wtiles = wt < ntiles ? wt : ntiles;
   }
-  // document mask: the block starts at its first row's document, each wave at
-  // its own first row's; keys below a row's document start are masked
+  // lower key bound (document mask and / or sliding window): the block starts
+  // at its first row's bound, each wave at its own first row's; keys below a
+  // row's bound are masked.  The bound grows with the row, so the wave's last
+  // row tells whether a tile needs the mask.  A window alone costs no loads.
   int t0 = 0, wt0 = 0, ds_row = 0, ds_wmax = 0;
-  if (CAUSAL && p.doc_start) {
-    const int* D = p.doc_start + (int64_t)b * p.sq;
+  if (CAUSAL && (p.doc_start || p.window > 0)) {
     const int r0 = mb * BMW < p.sq ? mb * BMW : p.sq - 1;
     const int w0 = m0 < p.sq ? m0 : p.sq - 1, w1 = m0 + 31 < p.sq ? m0 + 31 : p.sq - 1;
-    t0 = D[r0] / KT;
-    wt0 = D[w0] / KT;
-    ds_wmax = D[w1];
-    ds_row = D[qrow_c];
+    int l0 = 0, lw0 = 0;
+    if (p.doc_start) {
+      const int* D = p.doc_start + (int64_t)b * p.sq;
+      l0 = D[r0];
+      lw0 = D[w0];
+      ds_wmax = D[w1];
+      ds_row = D[qrow_c];
+    }
+    if (p.window > 0) {
+      const int wo = off - p.window + 1;  // row + wo: the row's first visible key
+      l0 = max(l0, r0 + wo);
+      lw0 = max(lw0, w0 + wo);
+      ds_wmax = max(ds_wmax, w1 + wo);
+      ds_row = max(ds_row, qrow_c + wo);
+    }
+    t0 = l0 / KT;
+    wt0 = lw0 / KT;
   }
 
   int srow[PPW], schunk[PPW];
@@ -233,10 +251,10 @@ __global__ __launch_bounds__(WAVES * 64, 8 / WAVES) void fa_fwd_k(const AttnPara
       if (need_mask) {
         // element i of s0 is key n0 + acc_row(i, h), of s1 that + 32: with
         // rc = acc_row(i, 0) the tests are rc <= hi and rc >= lo, one compare
-        // and one select per element (lo only under a document mask)
+        // and one select per element (lo only under a document mask / window)
         int hi = p.sk - 1 - n0 - 4 * h;
         if (CAUSAL) hi = min(hi, qrow + off - n0 - 4 * h);
-        if (CAUSAL && p.doc_start) {
+        if (CAUSAL && n0 < ds_wmax) {  // some row's lower bound lies inside or past this tile
           const int lo = ds_row - n0 - 4 * h;
 #pragma unroll
           for (int i = 0; i < 16; ++i) {

@@ -26,7 +26,9 @@
 //
 // With a device-side key count (DecodeParams::kv_len) the launch is
 // independent of the step, so the whole decode step can be captured once in
-// a hipGraph and replayed (inference/hip_graph.py).
+// a hipGraph and replayed (inference/hip_graph.py).  A sliding window
+// (DecodeParams::window) keeps the last `window` of the valid keys, bounded on
+// the device the same way.
 //
 // Used when it beats the FlashAttention forward on one query row (ops/attention.py
 // flash_attn_func): GQA/MQA (r >= 2: each K/V byte is read once, not r times)
@@ -69,7 +71,11 @@ __global__ __launch_bounds__(256) void decode_attn_k(const DecodeParams p) {
   const int h0 = hs * RH, nh = min(RH, r - h0);  // heads g*r + h0 .. + nh - 1
   const int k0 = chunk * DCH;
   const int sk = p.kv_len ? min(*p.kv_len, p.sk) : p.sk;
-  const int nk = min(DCH, sk - k0);  // <= 0: chunk past the cached length (graph decode)
+  // sliding window: only keys [klo, sk) count; a chunk wholly below klo leaves
+  // the empty partial of a chunk past the length, the straddling one masks
+  const int klo = p.window > 0 ? max(sk - p.window, 0) : 0;
+  // <= 0: chunk past the cached length (graph decode) or below the window
+  const int nk = k0 + DCH <= klo ? 0 : min(DCH, sk - k0);
   const float sl2 = p.scale * 1.4426950408889634f;
   const int nsplit = gridDim.x;
 
@@ -185,7 +191,7 @@ __global__ __launch_bounds__(256) void decode_attn_k(const DecodeParams p) {
       s[j] = __shfl(v[0], (lane % KPI) * LPK + (lane / KPI) * (LPK / NI), 64);
     }
     const int key = wave * KPW + lane;  // this lane's key within the chunk
-    const bool kon = lane < KPW && key < nk;
+    const bool kon = lane < KPW && key < nk && k0 + key >= klo;
     // chunk max per head
 #pragma unroll
     for (int j = 0; j < RH; ++j) {

@@ -149,6 +149,12 @@ struct AttnParams {
   // 3 ncu - 1 - lin in the heavy-first order) and every CU gets a heavy + a
   // light block.  0: plain heavy-first order.
   int pair_ncu;
+  // Sliding window (causal only; 0: none): key k is visible to query q iff
+  // q + coff - window < k <= q + coff.  A per-row lower key bound like
+  // doc_start (the two combine by max), computed in registers: the forward /
+  // dQ kernels start each query block at its first row's bound, the dK/dV
+  // kernel ends each key block at the last query that still sees it.
+  int window;
 };
 // pair_ncu for a causal grid of `grid` blocks of `waves` waves (0: no pairing);
 // fa_set_pairing(false) turns it off (tests: bitwise equal outputs either way)
@@ -211,6 +217,8 @@ struct DecodeParams {
   // combines the chunk partials and re-arms its counter
   unsigned* counters;
   int kpw;  // keys per wave: 64 / 16 / 8 (flash_decode_kpw picks; chunk = 4 kpw keys)
+  // sliding window (0: none): of the n valid keys only [max(0, n - window), n) count
+  int window;
 };
 int flash_decode_kpw(int b, int sk, int nq, int nkv);
 

@@ -170,6 +170,7 @@ class CoreAttention(MegatronModule):
             self.fp16, self.bf16, self.attn_mask_type, args.masked_softmax_fusion,
             attention_mask_func, self.attention_softmax_in_fp32, coeff)
         self.attention_dropout = torch.nn.Dropout(args.attention_dropout)
+        self.sliding_window = getattr(args, "sliding_window_size", None) or 0
 
     def forward(self, query_layer, key_layer, value_layer, attention_mask):
         # q: [sq, b, np, hn], k/v: [sk, b, np, hn]
@@ -180,11 +181,18 @@ class CoreAttention(MegatronModule):
         scores = torch.empty(b * np_, sq, sk, dtype=q.dtype, device=q.device)
         scores = torch.baddbmm(scores, q, k.transpose(1, 2), beta=0.0,
                                alpha=1.0 / self.norm_factor).view(b, np_, sq, sk)
-        if self.attn_mask_type == AttnMaskType.causal and sq != sk:
+        window = self.sliding_window if 0 < self.sliding_window < sk else 0
+        if self.attn_mask_type == AttnMaskType.causal and (sq != sk or window):
             # Inference with a KV cache: explicit bottom-right aligned mask.
+            # Sliding window: query i sees keys i + (sk - sq) - window + 1 .. i + (sk - sq).
             i = torch.arange(sq, device=q.device)[:, None]
             j = torch.arange(sk, device=q.device)[None, :]
-            attention_mask = (j > i + (sk - sq))[None, None]
+            causal_mask = (j > i + (sk - sq))[None, None]
+            if window:
+                causal_mask = causal_mask | (j <= i + (sk - sq) - window)[None, None]
+            if sq == sk and attention_mask is not None and attention_mask.dtype == torch.bool:
+                causal_mask = causal_mask | attention_mask
+            attention_mask = causal_mask
             probs = self.scale_mask_softmax.forward_torch_softmax(scores, attention_mask)
         else:
             probs = self.scale_mask_softmax(scores, attention_mask)
@@ -253,6 +261,11 @@ class ParallelAttention(MegatronModule):
         self.position_embedding_type = args.position_embedding_type
         self.rope_len = max(args.seq_length, args.max_position_embeddings or 0)
         self.rope_scaling = args.rope_scaling_factor
+        self.rope_theta = getattr(args, "rope_theta", None) or 10000.0
+        # sliding-window attention (Mistral): query i sees keys i - W + 1 .. i
+        self.sliding_window = getattr(args, "sliding_window_size", None) or 0
+        if self.sliding_window and attn_mask_type != AttnMaskType.causal:
+            raise AssertionError("a sliding window needs the causal mask")
         # context parallelism: this rank holds one contiguous sequence chunk
         self.cp_group = state.get_context_parallel_group() \
             if attention_type == AttnType.self_attn else None
@@ -262,7 +275,12 @@ class ParallelAttention(MegatronModule):
         if self.position_embedding_type != PositionEmbeddingType.rotary:
             return None
         return rope_table(self.hidden_size_per_attention_head, self.rope_len, device,
-                          scaling_factor=self.rope_scaling)
+                          theta=self.rope_theta, scaling_factor=self.rope_scaling)
+
+    def _window(self, sk):
+        """The window to pass for ``sk`` keys in hand: 0 when it covers them all
+        (the default attention paths run untouched)."""
+        return self.sliding_window if 0 < self.sliding_window < sk else 0
 
     def _split_qkv(self, mixed):
         sq, b = mixed.shape[:2]
@@ -310,7 +328,8 @@ class ParallelAttention(MegatronModule):
                                           attention_mask.dtype == torch.int32) else None
                 ctx = flash_attn_qkvpacked(mixed, self.num_groups_per_partition, self.q_per_group,
                                            self.hidden_size_per_attention_head, causal=True,
-                                           rope=rope, position_ids=position_ids, doc_bounds=docs)
+                                           rope=rope, position_ids=position_ids, doc_bounds=docs,
+                                           window=self._window(mixed.shape[0]))
         else:
             q, k, v = self._split_qkv(mixed)
             if rope is not None:
@@ -373,7 +392,7 @@ class ParallelAttention(MegatronModule):
             kc.index_copy_(0, ip.device_offset, k)
             vc.index_copy_(0, ip.device_offset, v)
             o = flash_decode_cached(q.transpose(0, 1), kc.transpose(0, 1), vc.transpose(0, 1),
-                                    ip.device_kv_len)
+                                    ip.device_kv_len, window=self._window(kc.shape[0]))
             return o.transpose(0, 1).reshape(sq, b, -1)
         kmem[s0:s0 + sq, b0:b0 + b] = k
         vmem[s0:s0 + sq, b0:b0 + b] = v
@@ -381,7 +400,7 @@ class ParallelAttention(MegatronModule):
         vals = vmem[:s0 + sq, b0:b0 + b]
         if self.use_flash_attn:
             o = flash_attn_func(q.transpose(0, 1), keys.transpose(0, 1), vals.transpose(0, 1),
-                                causal=True)
+                                causal=True, window=self._window(s0 + sq))
             return o.transpose(0, 1).reshape(sq, b, -1)
         return self.core_attention(q, self._expand_kv(keys), self._expand_kv(vals),
                                    attention_mask)
@@ -536,10 +555,11 @@ class ParallelTransformerLayer(MegatronModule):
                                     pq is not None)
         q4 = q.view(b, 1, ng * r, hd)
         if graph:
-            o = flash_decode_cached(q4, kc.transpose(0, 1), vc.transpose(0, 1), ip.device_kv_len)
+            o = flash_decode_cached(q4, kc.transpose(0, 1), vc.transpose(0, 1), ip.device_kv_len,
+                                    window=sa._window(kc.shape[0]))
         else:
             o = flash_attn_func(q4, kc[:s0 + 1].transpose(0, 1), vc[:s0 + 1].transpose(0, 1),
-                                causal=True)
+                                causal=True, window=sa._window(s0 + 1))
         # Row-parallel dense / fc2 under TP: each rank's product is a partial
         # sum; TP rank 0 alone adds the residual in its epilogue, so one
         # all-reduce of [b, H] yields partial sums + residual (reference

@@ -32,11 +32,15 @@ from .rope import rope_qkv_inplace, apply_rope_ref
 # --------------------------------------------------------------------------
 # Reference math (CPU path + test oracle)
 # --------------------------------------------------------------------------
-def attention_ref(q, k, v, causal=True, softmax_scale=None, return_lse=False, doc_bounds=None):
+def attention_ref(q, k, v, causal=True, softmax_scale=None, return_lse=False, doc_bounds=None,
+                  window=0):
     """q ``[b, sq, nq, d]``, k/v ``[b, sk, nkv, d]`` -> ``[b, sq, nq, d]`` (fp32 math).
 
     ``doc_bounds``: optional int32 ``[2, b, s]`` (document start, end) of
-    packed sequences: query i sees key j only if ``doc_start[i] <= j``."""
+    packed sequences: query i sees key j only if ``doc_start[i] <= j``.
+    ``window`` (W >= 1, causal only; 0: none): query i sees key j only if
+    ``i + (sk - sq) - W < j``."""
+    _check_window(window, causal)
     b, sq, nq, d = q.shape
     sk, nkv = k.shape[1], k.shape[2]
     scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(d)
@@ -49,6 +53,8 @@ def attention_ref(q, k, v, causal=True, softmax_scale=None, return_lse=False, do
         i = torch.arange(sq, device=q.device)[:, None]
         j = torch.arange(sk, device=q.device)[None, :]
         s = s.masked_fill(j > i + (sk - sq), float("-inf"))
+        if window:
+            s = s.masked_fill(j <= i + (sk - sq) - window, float("-inf"))
     if doc_bounds is not None:
         j = torch.arange(sk, device=q.device)[None, None, :]
         before = j < doc_bounds[0].to(q.device).long()[:, :, None]  # [b, sq, sk]
@@ -59,6 +65,11 @@ def attention_ref(q, k, v, causal=True, softmax_scale=None, return_lse=False, do
     if return_lse:
         return o, lse
     return o
+
+
+def _check_window(window, causal):
+    if window < 0 or (window and not causal):
+        raise ValueError("a sliding window must be >= 1 (0: none) and needs causal attention")
 
 
 def _split_qkv5(qkv5):
@@ -100,7 +111,7 @@ def _bsnd_strides(t, r):
 
 class _FlashQKVPackedFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, qkv, ng, r, hd, causal, scale, cos, sin, position_ids, docs):
+    def forward(ctx, qkv, ng, r, hd, causal, scale, cos, sin, position_ids, docs, window=0):
         s, b = qkv.shape[0], qkv.shape[1]
         qkv5 = qkv.view(s, b, ng, r + 2, hd)
         if position_ids is not None and position_ids.dtype != torch.int64:
@@ -114,9 +125,10 @@ class _FlashQKVPackedFn(torch.autograd.Function):
         os_ = (out.stride(1), out.stride(0), out.stride(2))
         ext().flash_attn_fwd(q, k, v, out, lse, b, s, s, nq, ng, hd,
                              list(qs), list(ks), list(ks), list(os_), bool(causal), float(scale),
-                             cos, sin, position_ids, docs)
+                             cos, sin, position_ids, docs, window=int(window))
         ctx.save_for_backward(qkv, out, lse, cos, sin, position_ids, docs)
         ctx.meta = (ng, r, hd, causal, scale)
+        ctx.window = int(window)
         return out.view(s, b, nq * hd)
 
     @staticmethod
@@ -135,41 +147,46 @@ class _FlashQKVPackedFn(torch.autograd.Function):
         os_ = (out.stride(1), out.stride(0), out.stride(2))
         ext().flash_attn_bwd(dout, q, k, v, out, lse, dq, dk, dv, b, s, s, nq, ng, hd,
                              list(qs), list(ks), list(ks), list(os_), bool(causal), float(scale),
-                             cos, sin, position_ids, docs)
-        return dqkv5.view(s, b, -1), None, None, None, None, None, None, None, None, None
+                             cos, sin, position_ids, docs, window=ctx.window)
+        return dqkv5.view(s, b, -1), None, None, None, None, None, None, None, None, None, None
 
 
-def _flash_decode(q, k, v, scale, kv_len=None):
+def _flash_decode(q, k, v, scale, kv_len=None, window=0):
     """sq == 1 against a KV cache (generation): split-key decode kernel
     (``csrc/flash_decode.hip``); no autograd.  ``kv_len``: optional device
     int32 tensor with the number of valid keys (k / v then span the whole
-    cache; the launch does not depend on the step, for hipGraph capture)."""
+    cache; the launch does not depend on the step, for hipGraph capture).
+    ``window``: only the last ``window`` valid keys count (0: all)."""
     b, _, nq, d = q.shape
     sk, nkv = k.shape[1], k.shape[2]
     r = nq // nkv
     out = torch.empty(b, 1, nq, d, dtype=q.dtype, device=q.device)
     ext().flash_decode(q, k, v, out, b, sk, nq, nkv, d, list(_bsnd_strides(q, r)),
                        list(_bsnd_strides(k, 1)[:3]), list(_bsnd_strides(v, 1)[:3]),
-                       [out.stride(0), out.stride(1), out.stride(2)], float(scale), kv_len)
+                       [out.stride(0), out.stride(1), out.stride(2)], float(scale), kv_len,
+                       window=int(window))
     return out
 
 
-def flash_decode_cached(q, k, v, kv_len, softmax_scale=None):
+def flash_decode_cached(q, k, v, kv_len, softmax_scale=None, window=0):
     """One query row per sequence against a whole KV cache ``k / v [b, smax,
-    nkv, d]`` of which the first ``kv_len`` (device int32) keys are valid."""
+    nkv, d]`` of which the first ``kv_len`` (device int32) keys are valid
+    (with ``window``: the last ``window`` of those)."""
+    _check_window(window, True)
     if not use_native(q):
         n = int(kv_len.reshape(-1)[0])
-        return attention_ref(q, k[:, :n], v[:, :n], False,
+        lo = max(n - window, 0) if window else 0
+        return attention_ref(q, k[:, lo:n], v[:, lo:n], False,
                              softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(q.shape[-1]))
     scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(q.shape[-1])
-    return _flash_decode(q, k, v, scale, kv_len)
+    return _flash_decode(q, k, v, scale, kv_len, window)
 
 
 class _FlashFn(torch.autograd.Function):
     """Separate q ``[b, sq, nq, d]``, k/v ``[b, sk, nkv, d]``."""
 
     @staticmethod
-    def forward(ctx, q, k, v, causal, scale):
+    def forward(ctx, q, k, v, causal, scale, window=0):
         b, sq, nq, d = q.shape
         sk, nkv = k.shape[1], k.shape[2]
         r = nq // nkv
@@ -181,9 +198,9 @@ class _FlashFn(torch.autograd.Function):
         os_ = (out.stride(0), out.stride(1), out.stride(2))
         ext().flash_attn_fwd(q, k, v, out, lse, b, sq, sk, nq, nkv, d,
                              list(qs), list(ks), list(vs), list(os_), bool(causal), float(scale),
-                             None, None, None, None)
+                             None, None, None, None, window=int(window))
         ctx.save_for_backward(q, k, v, out, lse)
-        ctx.causal, ctx.scale = causal, scale
+        ctx.causal, ctx.scale, ctx.window = causal, scale, int(window)
         return out
 
     @staticmethod
@@ -200,17 +217,21 @@ class _FlashFn(torch.autograd.Function):
         os_ = (out.stride(0), out.stride(1), out.stride(2))
         ext().flash_attn_bwd(dout, q, k, v, out, lse, dq, dk, dv, b, sq, sk, nq, nkv, d,
                              list(qs), list(ks), list(ks), list(os_), bool(ctx.causal),
-                             float(ctx.scale), None, None, None, None)
-        return dq, dk, dv, None, None
+                             float(ctx.scale), None, None, None, None, window=ctx.window)
+        return dq, dk, dv, None, None, None
 
 
 def flash_attn_qkvpacked(qkv, num_groups, q_per_group, head_dim, causal=True,
-                         softmax_scale=None, rope=None, position_ids=None, doc_bounds=None):
+                         softmax_scale=None, rope=None, position_ids=None, doc_bounds=None,
+                         window=0):
     """qkv ``[s, b, ng*(r+2)*hd]`` -> context ``[s, b, ng*r*hd]``.
 
     ``rope`` = (cos, sin) tables or None.  ``doc_bounds``: int32 ``[2, b, s]``
     document (start, end) per position for packed sequences
-    (``--reset_attention_mask``; :func:`utils.misc.doc_bounds`), or None."""
+    (``--reset_attention_mask``; :func:`utils.misc.doc_bounds`), or None.
+    ``window``: sliding-window size (query i sees keys ``i - window + 1 .. i``;
+    0: none)."""
+    _check_window(window, causal)
     scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(head_dim)
     cos, sin = rope if rope is not None else (None, None)
     if doc_bounds is not None:
@@ -219,7 +240,7 @@ def flash_attn_qkvpacked(qkv, num_groups, q_per_group, head_dim, causal=True,
         doc_bounds = doc_bounds.to(device=qkv.device, dtype=torch.int32).contiguous()
     if use_native(qkv):
         return _FlashQKVPackedFn.apply(qkv, num_groups, q_per_group, head_dim, causal, scale,
-                                       cos, sin, position_ids, doc_bounds)
+                                       cos, sin, position_ids, doc_bounds, window)
     s, b = qkv.shape[0], qkv.shape[1]
     qkv5 = qkv.view(s, b, num_groups, q_per_group + 2, head_dim)
     q, k, v = _split_qkv5(qkv5)
@@ -227,12 +248,15 @@ def flash_attn_qkvpacked(qkv, num_groups, q_per_group, head_dim, causal=True,
         q = apply_rope_ref(q, cos, sin, position_ids)
         k = apply_rope_ref(k, cos, sin, position_ids)
     o = attention_ref(q.transpose(0, 1), k.transpose(0, 1), v.transpose(0, 1), causal, scale,
-                      doc_bounds=doc_bounds)
+                      doc_bounds=doc_bounds, window=window)
     return o.transpose(0, 1).reshape(s, b, -1)
 
 
-def flash_attn_func(q, k, v, causal=True, softmax_scale=None):
-    """Separate tensors ``[b, s, n, d]`` (inference / generic callers)."""
+def flash_attn_func(q, k, v, causal=True, softmax_scale=None, window=0):
+    """Separate tensors ``[b, s, n, d]`` (inference / generic callers).
+    ``window``: sliding-window size relative to the bottom-right-aligned
+    diagonal (0: none)."""
+    _check_window(window, causal)
     scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(q.shape[-1])
     if use_native(q):
         b, sq, nq = q.shape[:3]
@@ -241,6 +265,7 @@ def flash_attn_func(q, k, v, causal=True, softmax_scale=None):
                 torch.is_grad_enabled() and (q.requires_grad or k.requires_grad or v.requires_grad)):
             # split-key decode: GQA/MQA reads each K/V byte once; small grids
             # spread over the chunks; short caches (profiles/r2f_decode_bench.txt)
-            return _flash_decode(q, k, v, scale)  # the last position sees every cached key
-        return _FlashFn.apply(q, k, v, causal, scale)
-    return attention_ref(q, k, v, causal, scale)
+            # the last position sees every cached key (of its window)
+            return _flash_decode(q, k, v, scale, window=window)
+        return _FlashFn.apply(q, k, v, causal, scale, window)
+    return attention_ref(q, k, v, causal, scale, window=window)

@@ -12,7 +12,7 @@ import torch
 
 from epfl_megatron_amd import get_args, get_tokenizer, get_timers, print_rank_0
 from epfl_megatron_amd.initialize import initialize_megatron
-from epfl_megatron_amd.models import FalconModel, GPTModel, LlamaModel, ModelType
+from epfl_megatron_amd.models import FalconModel, GPTModel, LlamaModel, MistralModel, ModelType
 from epfl_megatron_amd.parallel import tensor as tensor_parallel
 from epfl_megatron_amd.parallel.context import cp_token_mean, get_batch_on_this_cp_rank
 from epfl_megatron_amd.training import pretrain
@@ -28,6 +28,8 @@ def model_provider(pre_process=True, post_process=True):
         cls = GPTModel
     elif name == "falcon":
         cls = FalconModel
+    elif name == "mistral":
+        cls = MistralModel
     elif name in ("llama", "llama2"):
         cls = partial(LlamaModel, version=1 if name == "llama" else 2)
     else:
@@ -109,7 +111,7 @@ def train_valid_test_datasets_provider(train_val_test_num_samples):
 
 def extra_args(parser):
     group = parser.add_argument_group(title="validation set")
-    group.add_argument("--model_name", choices={"gpt", "llama", "falcon", "llama2"},
+    group.add_argument("--model_name", choices={"gpt", "llama", "falcon", "llama2", "mistral"},
                        default="gpt")
     group.add_argument("--model_type", choices={"encoder_or_decoder", "encoder_and_decoder"},
                        default="encoder_or_decoder")

@@ -45,7 +45,7 @@ def main(argv=None):
     parser = argparse.ArgumentParser(description="Megatron Checkpoint Utility Arguments",
                                      allow_abbrev=False, conflict_handler="resolve")
     parser.add_argument("--model_type", type=str, required=True,
-                        choices=["GPT", "BERT", "falcon", "llama", "llama2", "codellama"])
+                        choices=["GPT", "BERT", "falcon", "llama", "llama2", "codellama", "mistral"])
     parser.add_argument("--loader", type=str, default="megatron")
     parser.add_argument("--saver", type=str, default="megatron")
     parser.add_argument("--load_dir", type=str, required=True)

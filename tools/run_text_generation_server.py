@@ -15,7 +15,7 @@ from epfl_megatron_amd import get_args, print_rank_0  # noqa: E402
 from epfl_megatron_amd.checkpointing import load_checkpoint  # noqa: E402
 from epfl_megatron_amd.initialize import initialize_megatron  # noqa: E402
 from epfl_megatron_amd.models import (FalconModel, GPTModel, LlamaModel,  # noqa: E402
-                                      ModelType)
+                                      MistralModel, ModelType)
 from epfl_megatron_amd.training import get_model  # noqa: E402
 
 
@@ -24,7 +24,7 @@ def model_provider(pre_process=True, post_process=True):
     args = get_args()
     name = getattr(args, "model_name", "gpt")
     cls = {"gpt": GPTModel, "falcon": FalconModel, "llama": LlamaModel,
-           "llama2": LlamaModel}[name]
+           "llama2": LlamaModel, "mistral": MistralModel}[name]
     kw = {"version": 1 if name == "llama" else 2} if name in ("llama", "llama2") else {}
     return cls(num_tokentypes=0, parallel_output=False, pre_process=pre_process,
                post_process=post_process, **kw)
@@ -36,7 +36,8 @@ def add_text_generate_args(parser):
     g.add_argument("--top_p", type=float, default=0.0)
     g.add_argument("--top_k", type=int, default=0)
     g.add_argument("--out_seq_length", type=int, default=1024)
-    g.add_argument("--model_name", choices={"gpt", "llama", "llama2", "falcon"}, default="gpt")
+    g.add_argument("--model_name", choices={"gpt", "llama", "llama2", "falcon", "mistral"},
+                   default="gpt")
     g.add_argument("--port", type=int, default=5000)
     return parser
 

@@ -33,7 +33,8 @@ def is_megatron_path(path):
 
 def hf_provider(name, path, device):
     import transformers
-    cls = transformers.FalconForCausalLM if name == "falcon" else transformers.LlamaForCausalLM
+    cls = {"falcon": transformers.FalconForCausalLM,
+           "mistral": transformers.MistralForCausalLM}.get(name, transformers.LlamaForCausalLM)
     model = cls.from_pretrained(str(path), torch_dtype=torch.float32)
     return model.eval().requires_grad_(False).to(device)
 

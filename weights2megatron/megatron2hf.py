@@ -1,8 +1,8 @@
-"""Megatron checkpoint -> Hugging Face Llama / Falcon model directory.
+"""Megatron checkpoint -> Hugging Face Llama / Mistral / Falcon model directory.
 
 Reference CLI (``weights2megatron/megatron2hf.py:434-471``)::
 
-    python weights2megatron/megatron2hf.py --model {llama,llama2,falcon} \
+    python weights2megatron/megatron2hf.py --model {llama,llama2,mistral,falcon} \
         --input_dir CKPT --output_dir HF_DIR [--vocab_file tokenizer.model] \
         [--num_output_shards N] [--vocab_extra_ids_list ...] [--override_special_tokens k=v ...]
 
@@ -47,6 +47,26 @@ def write_llama_model(model_path, input_base_path, num_output_shards=1, norm_eps
     _save_hf(LlamaForCausalLM, cfg, sd, model_path, num_output_shards)
 
 
+def write_mistral_model(model_path, input_base_path, num_output_shards=1):
+    """``MistralForCausalLM``: Llama's weights; the config also carries the
+    checkpoint's sliding window and RoPE base."""
+    from transformers import MistralConfig, MistralForCausalLM
+    args, full, _ = load_full(input_base_path)
+    heads = args.num_attention_heads
+    kv = getattr(args, "num_attention_heads_kv", None) or heads
+    sd = megatron_to_hf_llama(full, heads, kv)
+    cfg = MistralConfig(vocab_size=sd["model.embed_tokens.weight"].shape[0],
+                        hidden_size=args.hidden_size, intermediate_size=args.ffn_hidden_size,
+                        num_attention_heads=heads, num_key_value_heads=kv,
+                        num_hidden_layers=args.num_layers,
+                        rms_norm_eps=getattr(args, "layernorm_epsilon", 1e-5),
+                        max_position_embeddings=args.max_position_embeddings,
+                        sliding_window=getattr(args, "sliding_window_size", None),
+                        rope_theta=float(getattr(args, "rope_theta", None) or 10000.0),
+                        tie_word_embeddings=False)
+    _save_hf(MistralForCausalLM, cfg, sd, model_path, num_output_shards)
+
+
 def write_falcon_model(model_path, input_base_path, num_output_shards=1):
     from transformers import FalconConfig, FalconForCausalLM
     args, full, _ = load_full(input_base_path)
@@ -82,7 +102,7 @@ def write_tokenizer(args):
     """SentencePiece tokenizer with the Megatron special tokens appended at the
     same ids (reference megatron2hf.py:352-431)."""
     from epfl_megatron_amd.tokenizer import build_tokenizer
-    if args.model in {"llama", "llama2"}:
+    if args.model in {"llama", "llama2", "mistral"}:
         from transformers import LlamaTokenizer
         vocab = args.vocab_file or os.path.join(args.input_dir, "tokenizer.model")
         if not os.path.isfile(vocab):
@@ -139,7 +159,8 @@ def main(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--input_dir", required=True, help="Megatron checkpoint directory")
     p.add_argument("--num_output_shards", type=int, default=1)
-    p.add_argument("--model", choices={"falcon", "llama", "llama2"}, default="llama2")
+    p.add_argument("--model", choices={"falcon", "llama", "llama2", "mistral"},
+                   default="llama2")
     p.add_argument("--output_dir", required=True)
     p.add_argument("--cache_dir", help="(unused: no network access)")
     p.add_argument("--vocab_file", type=str)
@@ -149,6 +170,8 @@ def main(argv=None):
     args = p.parse_args(argv)
     if args.model in {"llama", "llama2"}:
         write_llama_model(args.output_dir, args.input_dir, args.num_output_shards)
+    elif args.model == "mistral":
+        write_mistral_model(args.output_dir, args.input_dir, args.num_output_shards)
     else:
         write_falcon_model(args.output_dir, args.input_dir, args.num_output_shards)
     if not args.no_tokenizer:

@@ -2,8 +2,11 @@
 
 Reference CLI (``weights2megatron/weights2megatron.py:226-261``)::
 
-    python weights2megatron/weights2megatron.py {falcon,llama,llama2,codellama} \
+    python weights2megatron/weights2megatron.py {falcon,llama,llama2,codellama,mistral} \
         --size 7 --out OUT_DIR --cache-dir WEIGHTS_DIR
+
+``mistral`` takes a Hugging Face ``MistralForCausalLM`` directory; its shape,
+``sliding_window`` and ``rope_theta`` come from ``config.json``.
 
 ``--cache-dir`` (alias ``--model-path``) is a local directory: a Meta
 checkpoint (``consolidated.NN.pth`` + ``params.json``) or a Hugging Face
@@ -60,6 +63,30 @@ def convert_llama(src, size, version):
     return full, args, source
 
 
+def convert_mistral(src):
+    """HF Mistral directory: Llama's key layout (GQA, SwiGLU, RMSNorm) plus a
+    sliding window and a RoPE base, all read from ``config.json``."""
+    if hf_io.is_meta_dir(src):
+        raise ValueError("mistral conversion takes a Hugging Face directory (config.json)")
+    weights = hf_to_meta(hf_io.load_hf_state_dict(src))
+    cfg = hf_io.hf_config(src)
+    heads = cfg["num_attention_heads"]
+    kv = cfg.get("num_key_value_heads") or heads
+    emb = weights["tok_embeddings.weight"]
+    layers = max(int(k.split(".")[1]) for k in weights if k.startswith("layers.")) + 1
+    ffn = weights["layers.0.feed_forward.w1.weight"].shape[0]
+    full = llama_to_megatron(weights, heads, kv, "hf")
+    args = llama_args(layers, emb.shape[1], heads, ffn, kv, version=2, vocab=emb.shape[0],
+                      norm_eps=cfg.get("rms_norm_eps"),
+                      seq_length=cfg.get("max_position_embeddings"))
+    # (sliding_window null in config.json -- Mistral v0.2+ -- means no window)
+    # (newer transformers write the base under "rope_parameters")
+    theta = cfg.get("rope_theta") or (cfg.get("rope_parameters") or {}).get("rope_theta")
+    args.update(rope_theta=float(theta or 10000.0),
+                sliding_window_size=cfg.get("sliding_window"))
+    return full, args
+
+
 def convert_falcon(src):
     sd = hf_io.load_hf_state_dict(src)
     cfg = hf_io.hf_config(src)
@@ -84,6 +111,9 @@ def main(model_name="falcon", size=7, out=None, cache_dir=None):
     if model_name == "falcon":
         full, args = convert_falcon(str(cache_dir))
         source = "hf"
+    elif model_name == "mistral":
+        full, args = convert_mistral(str(cache_dir))
+        source = "hf"
     else:
         version = {"llama": 1, "llama2": 2, "codellama": 3}[model_name]
         full, args, source = convert_llama(str(cache_dir), size, version)
@@ -103,9 +133,9 @@ def main(model_name="falcon", size=7, out=None, cache_dir=None):
 
 
 if __name__ == "__main__":
-    p = argparse.ArgumentParser(description="Convert Meta/HF Llama or Falcon weights to a "
+    p = argparse.ArgumentParser(description="Convert Meta/HF Llama, Mistral or Falcon weights to a "
                                             "Megatron checkpoint")
-    p.add_argument("model", choices={"falcon", "llama", "llama2", "codellama"})
+    p.add_argument("model", choices={"falcon", "llama", "llama2", "codellama", "mistral"})
     p.add_argument("--size", default=7, type=int, choices={7, 13, 30, 34, 40, 65, 70})
     p.add_argument("--out", type=str, help="output checkpoint directory")
     p.add_argument("--cache-dir", "--model-path", dest="cache_dir", type=str,
