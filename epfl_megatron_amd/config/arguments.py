@@ -52,6 +52,12 @@ FLAG_TABLE = {
                    "(any TP / PP size: under PP every stage replays its own graph between an "
                    "eager receive and send; the whole-loop greedy decoder needs PP = 1; "
                    "inference/hip_graph.py)"),
+        _flag("--inference_fused_sampling", action="store_true",
+              help="sample the next token with one fused HIP launch (temperature, top-k or "
+                   "top-p and a Gumbel-max draw from Philox noise; ops/sampling.py) instead of "
+                   "the sort / softmax / cumsum / multinomial chain.  Same distribution, but "
+                   "a different random stream than torch.multinomial, and tokens tied with "
+                   "the top-p crossing one are all kept: opt-in"),
     ],
     "network size": [
         _flag("--num_layers", type=int, default=None),

@@ -922,6 +922,68 @@ void greedy_tail(const at::Tensor& logits, at::Tensor tokens, at::Tensor history
                    cur_stream());
 }
 
+// ---------------------------------------------------------------- sampling decode tail
+static int check_sample_logits(const at::Tensor& logits, const char* who) {
+  check_gpu(logits, "logits");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, who, ": logits [b, V], V contiguous");
+  const int dt = dtype_code(logits);
+  TORCH_CHECK(dt == ema::DT_BF16 || dt == ema::DT_F16 || dt == ema::DT_F32, who, ": dtype");
+  const int64_t b = logits.size(0), V = logits.size(1);
+  // b: the arrival counter keeps 16 bits for workgroups; V: the fixed-point
+  // softmax mass (2^40 per element) must sum below 2^63
+  TORCH_CHECK(b >= 1 && b < 65536 && V >= 1 && V <= (1ll << 22), who, ": shape");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0 &&
+                  (logits.stride(0) * logits.element_size()) % 16 == 0,
+              who, ": logits rows must be 16-byte aligned");
+  return dt;
+}
+
+// greedy_tail's arguments plus ctl int64 [6] = [seed, offset0, top_k,
+// vocab_limit, stop_id, n_stopped (written)] and fctl float32 [2] =
+// [temperature, top_p], both read on the device.
+void sample_tail(const at::Tensor& logits, at::Tensor tokens, at::Tensor history,
+                 at::Tensor step_idx, at::Tensor pos, at::Tensor slot, at::Tensor kv_len,
+                 at::Tensor counter, at::Tensor ctl, at::Tensor fctl) {
+  const int dt = check_sample_logits(logits, "sample_tail");
+  const int64_t b = logits.size(0), V = logits.size(1);
+  for (const at::Tensor* t : {&tokens, &history, &step_idx, &pos, &slot, &ctl})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kLong, "sample_tail: int64 state tensors");
+  TORCH_CHECK(kv_len.is_cuda() && kv_len.scalar_type() == at::kInt && kv_len.numel() >= 1 &&
+                  counter.is_cuda() && counter.scalar_type() == at::kInt && counter.numel() >= 1,
+              "sample_tail: kv_len / counter int32");
+  TORCH_CHECK(tokens.is_contiguous() && tokens.numel() == b && pos.is_contiguous() &&
+                  pos.numel() == b && history.dim() == 2 && history.size(0) == b &&
+                  history.stride(1) == 1 && step_idx.numel() >= 1 && slot.numel() >= 1,
+              "sample_tail: tokens / pos [b], history [b, H]");
+  TORCH_CHECK(ctl.is_contiguous() && ctl.numel() == 6 && fctl.is_cuda() &&
+                  fctl.scalar_type() == at::kFloat && fctl.is_contiguous() && fctl.numel() == 2,
+              "sample_tail: ctl int64 [6], fctl float32 [2]");
+  ema::sample_tail(logits.data_ptr(), logits.stride(0), (int)V, (int)b, dt,
+                   tokens.data_ptr<int64_t>(), history.data_ptr<int64_t>(), history.stride(0),
+                   history.size(1), step_idx.data_ptr<int64_t>(), pos.data_ptr<int64_t>(),
+                   slot.data_ptr<int64_t>(), kv_len.data_ptr<int>(),
+                   reinterpret_cast<unsigned*>(counter.data_ptr<int>()), ctl.data_ptr<int64_t>(),
+                   fctl.data_ptr<float>(), ema::SampleArgs{}, cur_stream());
+}
+
+// One draw per row of logits [b, V] into tokens int64 [b]; no tail state, the
+// settings are launch arguments (noise offset = offset, step 0).
+void sample_rows(const at::Tensor& logits, at::Tensor tokens, int64_t seed, int64_t offset,
+                 int64_t top_k, double top_p, double temperature, int64_t vocab_limit) {
+  const int dt = check_sample_logits(logits, "sample_rows");
+  const int64_t b = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(tokens.is_cuda() && tokens.scalar_type() == at::kLong && tokens.is_contiguous() &&
+                  tokens.numel() == b,
+              "sample_rows: tokens int64 [b]");
+  TORCH_CHECK(top_k >= 0 && top_k <= V && top_p >= 0.0 && top_p <= 1.0 && temperature > 0.0 &&
+                  !(top_k > 0 && top_p > 0.0),
+              "sample_rows: top_k / top_p / temperature");
+  ema::SampleArgs a{seed, offset, top_k, vocab_limit, -1, (float)temperature, (float)top_p};
+  ema::sample_tail(logits.data_ptr(), logits.stride(0), (int)V, (int)b, dt,
+                   tokens.data_ptr<int64_t>(), nullptr, 0, 0, nullptr, nullptr, nullptr, nullptr,
+                   nullptr, nullptr, nullptr, a, cur_stream());
+}
+
 // ---------------------------------------------------------------- bias-dropout-add
 at::Tensor bias_dropout_add_fwd(const at::Tensor& x, const c10::optional<at::Tensor>& x2,
                                 const c10::optional<at::Tensor>& bias, const at::Tensor& res,
@@ -1294,6 +1356,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fa_set_pairing", &ema::fa_set_pairing);
   m.def("fa_set_kv2", &ema::fa_set_kv2);
   m.def("greedy_tail", &greedy_tail);
+  m.def("sample_tail", &sample_tail);
+  m.def("sample_rows", &sample_rows, py::arg("logits"), py::arg("tokens"), py::arg("seed"),
+        py::arg("offset"), py::arg("top_k"), py::arg("top_p"), py::arg("temperature"),
+        py::arg("vocab_limit"));
   m.def("xgmi_create", &xgmi_create);
   m.def("xgmi_open", &xgmi_open);
   m.def("xgmi_all_reduce", &xgmi_all_reduce);

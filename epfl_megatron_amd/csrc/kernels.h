@@ -229,6 +229,21 @@ int flash_decode_kpw(int b, int sk, int nq, int nkv);
 void greedy_tail(const void* logits, int64_t ld, int V, int b, int dt, int64_t* tokens,
                  int64_t* history, int64_t hist_ld, int64_t* step_idx, int64_t* pos, int64_t* slot,
                  int* kv_len, unsigned* counter, hipStream_t s);
+// Sampling form of the tail (temperature, top-k or top-p, Gumbel-max draw from
+// Philox noise indexed by the device step; semantics in decode_tail.hip).
+// The settings are read on the device when ctl / fctl are given (int64
+// [seed, offset0, top_k, vocab_limit, stop_id, n_stopped], float [temperature,
+// top_p]: one captured graph serves any setting), else from `a`.  history ==
+// nullptr is the plain per-row form: only tokens[b] is written.  b < 65536
+// (the arrival counter carries the stopped-row count), V <= 2^22.
+struct SampleArgs {
+  int64_t seed, offset0, top_k, vocab_limit, stop_id;
+  float temperature, top_p;
+};
+void sample_tail(const void* logits, int64_t ld, int V, int b, int dt, int64_t* tokens,
+                 int64_t* history, int64_t hist_ld, int64_t hist_cols, int64_t* step_idx, int64_t* pos,
+                 int64_t* slot, int* kv_len, unsigned* counter, int64_t* ctl, const float* fctl, SampleArgs a,
+                 hipStream_t s);
 int flash_decode_splits(int sk, int kpw);
 int flash_decode_counters(int b, int nq, int nkv);
 void flash_decode(const DecodeParams& p, int dt, hipStream_t s);

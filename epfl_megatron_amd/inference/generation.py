@@ -11,6 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import global_vars
+from ..ops.sampling import sample_fused
 from ..parallel import state
 from ..utils.misc import get_ltor_masks_and_position_ids
 from .beam_utils import BeamHypotheses
@@ -74,6 +75,7 @@ def generate_tokens_probs_and_return_on_first_stage(
     max_len = tokens.size(1)
     _check_budget(args, max_len, b)
     step = ForwardStep(model, b, max_len)
+    fused_sampling = getattr(args, "inference_fused_sampling", False)
     termination_id = getattr(args, "eos_id", None)
     if termination_id is None:
         termination_id = tokenizer.eod
@@ -99,8 +101,13 @@ def generate_tokens_probs_and_return_on_first_stage(
                 logits = logits.float()
                 if prevent_newline_after_colon and colon is not None and eol is not None:
                     logits[toks[:, -1] == colon, -1, eol] = -1e10
-                new = sample(logits[:, -1, :].contiguous(), top_k=top_k, top_p=top_p,
-                             temperature=temperature, vocab_size=tokenizer.vocab_size)
+                if fused_sampling:  # one HIP launch (ops/sampling.py), reads the view
+                    new = sample_fused(logits[:, -1, :], top_k=top_k, top_p=top_p,
+                                       temperature=temperature,
+                                       vocab_size=tokenizer.vocab_size).to(tokens.device)
+                else:
+                    new = sample(logits[:, -1, :].contiguous(), top_k=top_k, top_p=top_p,
+                                 temperature=temperature, vocab_size=tokenizer.vocab_size)
                 if top_p > 0.0 and top_p_decay > 0.0:
                     top_p = max(top_p * top_p_decay, top_p_bound) if top_p_bound > 0.0 \
                         else top_p * top_p_decay

@@ -18,6 +18,12 @@ What makes the step capturable: nothing in it depends on the step on the host.
   * ``GraphedGreedyDecoder``: greedy selection (argmax), the position /
     slot / length increments and the write into the generated-token history
     are part of the graph (no host work per token at all);
+  * ``GraphedSamplingDecoder``: the same loop for requests with a
+    temperature, ``top_k`` or ``top_p``: the filter and a Gumbel-max draw
+    run in the tail kernel (``sample_tail_k``, ``csrc/decode_tail.hip``), its
+    noise indexed by the device step counter, so every replay draws fresh
+    noise; the settings and the Philox (seed, offset) are device tensors that
+    ``start()`` writes: one captured graph serves any sampling setting;
   * ``GraphedDecodeForward`` (``--inference_hip_graph``, used by
     ``ForwardStep`` and so by the text-generation API and server): only the
     forward is replayed, sampling and stop conditions stay eager.
@@ -38,8 +44,11 @@ state is received into a static buffer the graph reads, the static output is
 sent after the replay), as the reference's PP forward step does
 (``megatron/text_generation/forward_step.py:153-204``).  The launch-bound part
 (tens of small kernels per layer) is in the graph; one send / recv per stage
-per token is not.  ``GraphedGreedyDecoder`` (argmax and the token feedback in
-the graph) needs the whole model on the rank: PP = 1.  Without a GPU the
+per token is not.  ``GraphedGreedyDecoder`` and ``GraphedSamplingDecoder``
+(token selection and feedback in the graph) need the whole model on the rank:
+PP = 1.  Under TP > 1 the sampling decoder broadcasts TP rank 0's (seed,
+offset) in ``start()``, so every rank draws the same token from the gathered
+logits.  Without a GPU the
 same static-buffer step runs eagerly (the CPU / gloo tests drive the PP
 plumbing through it).
 
@@ -231,3 +240,91 @@ class GraphedGreedyDecoder:
         self.steps_done += 1
         self.ip.sequence_len_offset = self.base + self.steps_done
         return self.tokens
+
+
+def broadcast_seed_offset(seed, offset, device, group=None, src=None):
+    """TP rank 0's ``(seed, offset)`` on every rank of the tensor-parallel
+    group: all ranks hold the same gathered logits, and with the same noise
+    they pick the same token.  ``group`` / ``src`` default to the TP group and
+    its first rank."""
+    if group is None:
+        if not state.model_parallel_is_initialized() or \
+                state.get_tensor_model_parallel_world_size() == 1:
+            return seed, offset
+        group = state.get_tensor_model_parallel_group()
+        src = state.get_tensor_model_parallel_src_rank()
+    from ..parallel import comm
+    t = torch.tensor([seed, offset], dtype=torch.long, device=device)
+    comm.broadcast(t, src, group=group)
+    seed, offset = t.tolist()
+    return seed, offset
+
+
+class GraphedSamplingDecoder(GraphedGreedyDecoder):
+    """``GraphedGreedyDecoder`` with the sampling tail (``sample_tail_k``,
+    ``csrc/decode_tail.hip``; semantics in ``ops/sampling.py``) in place of the
+    argmax: temperature and top-k or top-p, an optional stop token, still one
+    launch after the forward and no host work per token.
+
+    Usage::
+
+        dec = GraphedSamplingDecoder(model, ip, batch, max_new_tokens)
+        dec.start(next_tokens, position, top_k=0, top_p=0.9, temperature=0.8, stop_id=-1)
+        for _ in range(n):
+            dec.step()
+        tokens = dec.history[:, :n]
+        dec.n_stopped                  # rows that emitted stop_id in the last step (syncs)
+
+    Every setting lives in two device tensors the kernel reads, ``ctl`` int64
+    ``[seed, offset0, top_k, vocab_limit, stop_id, n_stopped]`` and ``fctl``
+    float32 ``[temperature, top_p]``, so a later ``start()`` with other settings
+    replays the same captured graph.  Step ``s`` draws its noise at Philox
+    offset ``offset0 + s``; ``start()`` takes ``(seed, offset0)`` from the CUDA
+    generator (TP rank 0's, under tensor parallelism) and advances the
+    generator past every offset the generation can use."""
+
+    def __init__(self, model, inference_params, batch, max_new_tokens, vocab_size=None):
+        super().__init__(model, inference_params, batch, max_new_tokens)
+        dev = self.tokens.device
+        self.vocab_size = vocab_size
+        self.ctl = torch.zeros(6, dtype=torch.long, device=dev)
+        self.fctl = torch.ones(2, dtype=torch.float32, device=dev)
+        self.seed = self.offset0 = None
+
+    def _body(self):
+        logits = self._forward()
+        last = logits[:, -1]
+        if not self._fused_tail(last):
+            raise RuntimeError("the sampling tail needs bf16 / fp16 / fp32 logits on the GPU "
+                               "with 16-byte aligned rows")
+        from ..ops._ext import ext
+        ext().sample_tail(last, self.tokens.view(-1), self.history, self.step_idx,
+                          self.pos.view(-1), self.ip.device_offset, self.ip.device_kv_len,
+                          self.tail_counter, self.ctl, self.fctl)
+        return logits
+
+    def start(self, next_tokens, position, top_k=0, top_p=0.0, temperature=1.0, stop_id=-1):
+        """As ``GraphedGreedyDecoder.start`` plus the sampling settings of this
+        generation (one setting per batch, as the text-generation API has)."""
+        if top_k < 0 or (top_k > 0 and top_p != 0.0):
+            raise AssertionError("cannot set both top-k and top-p samplings")
+        if not 0.0 <= top_p <= 1.0:
+            raise AssertionError("top-p should be in (0, 1]")
+        if not temperature > 0.0:
+            raise AssertionError("temperature should be positive")
+        dev = self.tokens.device
+        gen = torch.cuda.default_generators[dev.index]
+        seed, offset0 = gen.initial_seed(), gen.get_offset()
+        # one Philox offset per step; the generator moves in multiples of 4
+        gen.set_offset(offset0 + (self.max_new + 4) // 4 * 4)
+        self.seed, self.offset0 = broadcast_seed_offset(seed, offset0, dev)
+        ctl = torch.tensor([self.seed, self.offset0, top_k, self.vocab_size or 0, stop_id, 0],
+                           dtype=torch.long)
+        self.ctl.copy_(ctl, non_blocking=False)
+        self.fctl.copy_(torch.tensor([temperature, top_p], dtype=torch.float32))
+        super().start(next_tokens, position)
+
+    @property
+    def n_stopped(self):
+        """Rows that emitted ``stop_id`` in the last step (reads the device)."""
+        return int(self.ctl[5].item())
