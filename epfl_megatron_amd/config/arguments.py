@@ -52,6 +52,12 @@ FLAG_TABLE = {
                    "(any TP / PP size: under PP every stage replays its own graph between an "
                    "eager receive and send; the whole-loop greedy decoder needs PP = 1; "
                    "inference/hip_graph.py)"),
+        _flag("--inference_fp8_weights", action="store_true",
+              help="FP8 weight-only decode: the fused decode layer streams the QKV, dense, fc1 "
+                   "and fc2 weights as per-row-scaled e4m3 copies (ops/fp8_weights.py; half "
+                   "the bytes per decode step).  Activations, KV cache, LM head, prefill and "
+                   "the 16-bit parameters are unchanged.  Changes the outputs by the weight "
+                   "quantisation error: opt-in"),
         _flag("--inference_fused_sampling", action="store_true",
               help="sample the next token with one fused HIP launch (temperature, top-k or "
                    "top-p and a Gumbel-max draw from Philox noise; ops/sampling.py) instead of "

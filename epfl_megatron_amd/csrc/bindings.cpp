@@ -675,12 +675,29 @@ bool skinny_gemm_supported(int64_t M, int64_t N, int64_t K) {
   return ema::skinny_gemm_supported(M, N, K);
 }
 
+// FP8 weight-only decode (ops/fp8_weights.py): w holds e4m3fn values in the
+// packed FP8 layout and w_scale one fp32 scale per W row.  Returns the scale
+// pointer for SkinnyArgs::w_scale.
+static const float* skinny_fp8_scale(const at::Tensor& x, const at::Tensor& w,
+                                     const at::Tensor& w_scale, bool packed) {
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == at::kFloat8_e4m3fn,
+              "skinny fp8: w must be float8_e4m3fn when w_scale is given");
+  TORCH_CHECK(packed && x.size(1) % 256 == 0,
+              "skinny fp8: only packed weights with K % 256 == 0 (ops/fp8_weights.py)");
+  TORCH_CHECK(w_scale.is_cuda() && w_scale.scalar_type() == at::kFloat && w_scale.dim() == 1 &&
+              w_scale.is_contiguous() && w_scale.size(0) == w.size(0),
+              "skinny fp8: w_scale must be contiguous fp32 with one entry per W row");
+  check_vec_aligned(w_scale, "w_scale");
+  return w_scale.data_ptr<float>();
+}
+
 // x [M, K] @ w[N, K]^T -> [M, N]
-at::Tensor skinny_gemm(const at::Tensor& x, const at::Tensor& w, bool packed) {
+at::Tensor skinny_gemm(const at::Tensor& x, const at::Tensor& w, bool packed,
+                       const c10::optional<at::Tensor>& w_scale) {
   check_gpu(x, "x");
   TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1), "skinny_gemm: shapes");
   TORCH_CHECK(x.is_contiguous() && w.is_contiguous(), "skinny_gemm: contiguous operands");
-  TORCH_CHECK(x.scalar_type() == w.scalar_type(), "skinny_gemm: dtype mismatch");
+  TORCH_CHECK(w_scale || x.scalar_type() == w.scalar_type(), "skinny_gemm: dtype mismatch");
   const int dt = dtype_code(x);
   TORCH_CHECK(dt == ema::DT_BF16 || dt == ema::DT_F16, "skinny_gemm: bf16/fp16 only");
   const int64_t M = x.size(0), N = w.size(0), K = x.size(1);
@@ -698,6 +715,7 @@ at::Tensor skinny_gemm(const at::Tensor& x, const at::Tensor& w, bool packed) {
   p.K = (int)K;
   p.ldy = N;
   p.packed = packed ? 1 : 0;
+  if (w_scale) p.w_scale = skinny_fp8_scale(x, w, *w_scale, packed);
   ema::skinny_gemm_ex(p, 0, dt, cur_stream());
   return y;
 }
@@ -708,11 +726,11 @@ at::Tensor skinny_gemm(const at::Tensor& x, const at::Tensor& w, bool packed) {
 // 3 QKV (-> q [M, nq * hd]; k / v written into the cache slot).
 static ema::SkinnyArgs skinny_args(const at::Tensor& x, const at::Tensor& w,
                                    const c10::optional<at::Tensor>& norm_w, double eps,
-                                   bool packed) {
+                                   bool packed, const c10::optional<at::Tensor>& w_scale) {
   check_gpu(x, "x");
   TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1), "skinny: shapes");
   TORCH_CHECK(x.is_contiguous() && w.is_contiguous(), "skinny: contiguous operands");
-  TORCH_CHECK(x.scalar_type() == w.scalar_type(), "skinny: dtype mismatch");
+  TORCH_CHECK(w_scale || x.scalar_type() == w.scalar_type(), "skinny: dtype mismatch");
   const int dt = dtype_code(x);
   TORCH_CHECK(dt == ema::DT_BF16 || dt == ema::DT_F16, "skinny: bf16/fp16 only");
   check_vec_aligned(x, "x");
@@ -724,6 +742,7 @@ static ema::SkinnyArgs skinny_args(const at::Tensor& x, const at::Tensor& w,
   p.K = (int)x.size(1);
   TORCH_CHECK(!packed || p.K % 256 == 0, "skinny: packed weights need K % 256 == 0");
   p.packed = packed ? 1 : 0;
+  if (w_scale) p.w_scale = skinny_fp8_scale(x, w, *w_scale, packed);
   if (norm_w) {
     TORCH_CHECK(norm_w->is_cuda() && norm_w->is_contiguous() && norm_w->numel() == p.K &&
                 norm_w->scalar_type() == x.scalar_type(), "skinny: norm weight must be [K], x dtype");
@@ -735,8 +754,9 @@ static ema::SkinnyArgs skinny_args(const at::Tensor& x, const at::Tensor& w,
 
 at::Tensor skinny_norm_gemm(const at::Tensor& x, const at::Tensor& w,
                             const c10::optional<at::Tensor>& norm_w, double eps,
-                            const c10::optional<at::Tensor>& res, bool packed) {
-  auto p = skinny_args(x, w, norm_w, eps, packed);
+                            const c10::optional<at::Tensor>& res, bool packed,
+                            const c10::optional<at::Tensor>& w_scale) {
+  auto p = skinny_args(x, w, norm_w, eps, packed, w_scale);
   const int64_t N = w.size(0);
   TORCH_CHECK(ema::skinny_gemm_supported(p.M, N, p.K), "skinny: unsupported shape");
   auto y = at::empty({p.M, N}, x.options());
@@ -759,8 +779,9 @@ at::Tensor skinny_norm_gemm(const at::Tensor& x, const at::Tensor& w,
 
 at::Tensor skinny_norm_glu(const at::Tensor& x, const at::Tensor& w1,
                            const c10::optional<at::Tensor>& norm_w, double eps, int64_t kind,
-                           bool packed, int64_t packed_tail) {
-  auto p = skinny_args(x, w1, norm_w, eps, packed);
+                           bool packed, int64_t packed_tail,
+                           const c10::optional<at::Tensor>& w_scale) {
+  auto p = skinny_args(x, w1, norm_w, eps, packed, w_scale);
   const int64_t F = w1.size(0) / 2;
   TORCH_CHECK(w1.size(0) == 2 * F && F % 8 == 0 &&
               ema::skinny_gemm_supported(p.M, 2 * F, p.K), "skinny glu: unsupported shape");
@@ -784,8 +805,9 @@ at::Tensor skinny_qkv_rope_cache(const at::Tensor& x, const at::Tensor& w,
                                  int64_t r, int64_t hd, const at::Tensor& cos,
                                  const at::Tensor& sin, const at::Tensor& pos, at::Tensor kcache,
                                  at::Tensor vcache, const c10::optional<at::Tensor>& slot_t,
-                                 int64_t slot, bool packed) {
-  auto p = skinny_args(x, w, norm_w, eps, packed);
+                                 int64_t slot, bool packed,
+                                 const c10::optional<at::Tensor>& w_scale) {
+  auto p = skinny_args(x, w, norm_w, eps, packed, w_scale);
   const int64_t N = w.size(0);
   TORCH_CHECK(N == ng * (r + 2) * hd && hd % 8 == 0, "skinny qkv: w rows != ng * (r + 2) * hd");
   TORCH_CHECK(ema::skinny_gemm_supported(p.M, N, p.K), "skinny qkv: unsupported shape");
@@ -1380,18 +1402,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("b"), py::arg("sk"), py::arg("nq"), py::arg("nkv"), py::arg("hd"), py::arg("qs"),
         py::arg("ks"), py::arg("vs"), py::arg("os"), py::arg("scale"), py::arg("kv_len"),
         py::arg("kpw") = 0, py::arg("window") = 0);
-  m.def("skinny_gemm", &skinny_gemm, py::arg("x"), py::arg("w"), py::arg("packed") = false);
+  m.def("skinny_gemm", &skinny_gemm, py::arg("x"), py::arg("w"), py::arg("packed") = false,
+        py::arg("w_scale") = py::none());
   m.def("skinny_gemm_supported", &skinny_gemm_supported);
   m.def("skinny_norm_gemm", &skinny_norm_gemm, py::arg("x"), py::arg("w"), py::arg("norm_w"),
-        py::arg("eps"), py::arg("res"), py::arg("packed") = false);
+        py::arg("eps"), py::arg("res"), py::arg("packed") = false, py::arg("w_scale") = py::none());
   m.def("skinny_norm_glu", &skinny_norm_glu, py::arg("x"), py::arg("w1"), py::arg("norm_w"),
-        py::arg("eps"), py::arg("kind"), py::arg("packed") = false, py::arg("packed_tail") = 0);
+        py::arg("eps"), py::arg("kind"), py::arg("packed") = false, py::arg("packed_tail") = 0,
+        py::arg("w_scale") = py::none());
   m.def("skinny_glu_half_tail", &ema::skinny_glu_half_tail, py::arg("F"), py::arg("K"),
         py::arg("norm"), py::arg("M") = 1);
   m.def("skinny_qkv_rope_cache", &skinny_qkv_rope_cache, py::arg("x"), py::arg("w"),
         py::arg("norm_w"), py::arg("eps"), py::arg("ng"), py::arg("r"), py::arg("hd"),
         py::arg("cos"), py::arg("sin"), py::arg("pos"), py::arg("kcache"), py::arg("vcache"),
-        py::arg("slot_t"), py::arg("slot"), py::arg("packed") = false);
+        py::arg("slot_t"), py::arg("slot"), py::arg("packed") = false,
+        py::arg("w_scale") = py::none());
   m.def("transpose16", &transpose16);
   m.def("transpose16_supported", &transpose16_supported);
 }

@@ -348,6 +348,11 @@ struct SkinnyArgs {
   const int64_t* slot_ptr;  // device slot index (graph decode) or nullptr: `slot`
   int64_t slot;
   int packed;           // 1: w is in the decode-packed layout (skinny_pack, K % 256 == 0)
+  // FP8 weight-only decode: non-null = w holds OCP e4m3fn bytes in the packed
+  // FP8 layout (ops/fp8_weights.py) and w_scale[row] (fp32, original W row
+  // order: [N], GLU [2N] up rows then gate rows) multiplies the fp32 sums
+  // before the epilogue's first rounding.  nullptr: the 16-bit paths.
+  const float* w_scale;
 };
 void skinny_gemm_ex(const SkinnyArgs& p, int epi, int dt, hipStream_t s);
 int skinny_glu_half_tail(int64_t F, int64_t K, bool norm, int64_t M);

@@ -44,6 +44,16 @@
 // the Llama-2-7B shapes (scripts/gemv_layout_bench.hip,
 // profiles/r4m_gemv_layout.txt).  The k index a lane feeds is unchanged, so X /
 // gamma loads and every epilogue are layout-independent.
+//
+// FP8 weights (p.w_scale != nullptr; W8 forms, packed 8-wave only): W is OCP
+// e4m3fn with one fp32 scale per W row (ops/fp8_weights.py).  The packed
+// stream keeps the 16-B loads: one lane's piece holds its 8 e4m3 values of
+// TWO consecutive k-steps (a ring slot = one 1 KiB unit per wave, lane L at
+// byte 16 L; an odd last k-step is one 8-B piece per lane).  Each piece is
+// expanded to two T x8 A fragments (v_cvt_pk_f32_fp8 + the exact f32 -> T
+// conversion) right before its two MFMAs, so the MFMAs, the k order and every
+// rounding are those of the 16-bit forms on the same values; the epilogues
+// multiply the reduced fp32 tile by the row scales before their first rounding.
 #include <cstdlib>
 #include <type_traits>
 
@@ -56,6 +66,9 @@ namespace ema {
 namespace {
 
 typedef __attribute__((ext_vector_type(4))) float f4;
+typedef __attribute__((ext_vector_type(2))) float f2;
+typedef __attribute__((ext_vector_type(4))) int i4;
+typedef __attribute__((ext_vector_type(2))) int i2;
 
 enum { EPI_PLAIN = 0, EPI_RES = 1, EPI_GLU = 2, EPI_QKV = 3 };
 
@@ -63,6 +76,18 @@ template <typename T>
 __device__ __forceinline__ f4 mfma16x16x32(typename fa::MT<T>::x8 a, typename fa::MT<T>::x8 b, f4 c) {
   if constexpr (__is_same(T, bf16)) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
   else return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
+}
+
+// 8 e4m3fn bytes (k order: lo bytes 0-3, hi bytes 0-3) -> one A fragment of T;
+// every e4m3 value is exact in bf16 and fp16
+template <typename T>
+__device__ __forceinline__ typename fa::MT<T>::x8 fp8x8(int lo, int hi) {
+  typename fa::MT<T>::x8 o;
+  const f2 c0 = __builtin_amdgcn_cvt_pk_f32_fp8(lo, false), c1 = __builtin_amdgcn_cvt_pk_f32_fp8(lo, true);
+  const f2 c2 = __builtin_amdgcn_cvt_pk_f32_fp8(hi, false), c3 = __builtin_amdgcn_cvt_pk_f32_fp8(hi, true);
+  o[0] = (T)c0[0]; o[1] = (T)c0[1]; o[2] = (T)c1[0]; o[3] = (T)c1[1];
+  o[4] = (T)c2[0]; o[5] = (T)c2[1]; o[6] = (T)c3[0]; o[7] = (T)c3[1];
+  return o;
 }
 
 // W row fed to MFMA row r of workgroup n-block `blk`
@@ -85,7 +110,36 @@ struct EpiPre {
   float c[2] = {0.f, 0.f}, s[2] = {0.f, 0.f};
   int pos = 0;       // (32-bit: two row blocks' 64-bit positions and slots spilled)
   int64_t slot = 0;  // uniform: scalar registers
+  f4 sc = {1.f, 1.f, 1.f, 1.f};  // W8: the scales of the lane's 4 W rows (epi_scale)
 };
+
+// W8: the reduced fp32 tile times the row scales, in front of the epilogue's
+// first rounding.  The product is handed on as an opaque value so that the
+// epilogue compiles from the same expressions as in the 16-bit forms: fused
+// with the multiply, hipcc contracted other products of the rotary rotation
+// into FMAs than it does there, and a q element that cancels to ~1e-5 of its
+// terms came out one ulp apart.
+__device__ __forceinline__ f4 scale_tile(f4 t, const f4& sc) {
+  t *= sc;
+  asm volatile("" : "+v"(t));
+  return t;
+}
+
+// W8: the fp32 scales of the 4 W rows whose sums this lane holds (MFMA rows
+// 4 (lane >> 4) + i: consecutive W rows in every form, 16-B aligned)
+template <int EPI>
+__device__ __forceinline__ f4 epi_scale(const SkinnyArgs& p, int blk, int half, int lane) {
+  const int nr = 4 * (lane >> 4);
+  int64_t row;
+  if constexpr (EPI == EPI_GLU) {
+    // half unit: MFMA rows 0-3 / 8-11 (4-7 / 12-15 duplicate them) = features 8 blk + 4 half ..
+    if (half < 0) row = w_row<EPI>(blk, nr, p.N);
+    else row = (nr < 8 ? 0 : (int64_t)p.N) + (int64_t)blk * 8 + 4 * half;
+  } else {
+    row = (int64_t)blk * 16 + nr;
+  }
+  return *reinterpret_cast<const f4*>(p.w_scale + row);
+}
 
 template <typename T, int EPI>
 __device__ __forceinline__ void epi_init(const SkinnyArgs& p, int lane, EpiPre<T, EPI>& e,
@@ -191,15 +245,25 @@ __device__ __forceinline__ void epilogue(const SkinnyArgs& p, int blk, const f4&
 
 // MB: 16-row blocks of X (1: M <= 16; 2: M <= 32 -- every W fragment feeds
 // one MFMA per row block, so the weight stream is read once for 32 rows).
-template <typename T, int WAVES, bool NORM, int EPI, int ACT, bool PACKED, int MB>
+// W8: e4m3 weights, a ring slot = one 16-B piece = SPU = 2 k-steps.
+template <typename T, int WAVES, bool NORM, int EPI, int ACT, bool PACKED, int MB, bool W8 = false>
 __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) {
   typedef typename fa::MT<T>::x8 x8;
+  typedef std::conditional_t<W8, i4, x8> wslot;
+  static_assert(!W8 || PACKED, "e4m3 weights come decode-packed only");
+  constexpr int SPU = W8 ? 2 : 1;  // k-steps per ring slot
   // (a 16-deep ring for one row block measured the same: fc2 K = 11008 at
   // 16 rows 23.2 vs 23.0 us, profiles/r4al_skinny_u16.txt)
   // two un-normed row blocks (fc2 at 17-32 rows, K = 11008: 43 k-steps per
   // wave = 3 x 14 + 1): 14 deep, 28.6 / 33.4 us at 24 / 32 rows vs 29.7 / 34.8
   // at 8 (profiles/r4ar_skinny_u14.txt)
-  constexpr int U = MB == 2 && !NORM ? 14 : SKINNY_U;
+  // W8: the same ring registers hold twice the k-steps, so one row block runs
+  // 16 steps (8 pieces = the 8 KiB per wave of the 16-bit ring) in flight; two
+  // row blocks keep the 16-bit forms' step counts (their X fragments are the
+  // register cost) in half the pieces
+  constexpr int U = MB == 2 && !NORM ? 14 : W8 && MB == 1 ? 2 * SKINNY_U : SKINNY_U;
+  constexpr int US = U / SPU;  // ring slots
+  static_assert(U % SPU == 0, "ring slots hold whole pieces");
   __shared__ f4 part[WAVES][MB][64];
   __shared__ float ssq[WAVES][16 * MB];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -215,6 +279,18 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) 
   static_assert(!PACKED || WAVES == 8, "the packed layout is cut for 8 waves");
   const T* wr = PACKED ? w + ((int64_t)blockIdx.x * WAVES + wave) * steps * 512 + 8 * lane
                        : w + w_row<EPI>(blockIdx.x, r, N) * K + kbeg + kc;
+  // W8: the (block, wave) stream is steps x 512 B; the piece of k-steps s, s + 1
+  // (s even) at byte 512 s + 16 lane, an odd last step at 512 s + 8 lane
+  const unsigned char* w8 =
+      (const unsigned char*)p.w + ((int64_t)blockIdx.x * WAVES + wave) * steps * 512;
+  auto wload = [&](int s) -> wslot {  // ring slot holding k-step s (W8: s even, and s + 1)
+    if constexpr (W8) return __builtin_nontemporal_load(reinterpret_cast<const i4*>(w8 + 512 * s + 16 * lane));
+    else return __builtin_nontemporal_load(reinterpret_cast<const x8*>(wr + WS * s));
+  };
+  auto afrag = [&](const wslot& v, int h) -> x8 {  // A fragment of the slot's k-step h
+    if constexpr (W8) return fp8x8<T>(v[2 * h], v[2 * h + 1]);
+    else return v;
+  };
   bool xon[MB];
   const T* xr[MB];
 #pragma unroll
@@ -231,15 +307,21 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) 
   // loads stay in flight through the whole stream.  Issued BEFORE the RMSNorm
   // prologue: the weight stream starts at kernel entry, not after the norm's
   // reduction and barrier.
-  x8 a[U], xv[MB][U], gv[U];
+  wslot a[US];
+  x8 xv[MB][U], gv[U];
   if (nblk > 0) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      a[u] = __builtin_nontemporal_load(reinterpret_cast<const x8*>(wr + WS * u));
+      if (u % SPU == 0) a[u / SPU] = wload(u);
 #pragma unroll
       for (int mb = 0; mb < MB; ++mb) xv[mb][u] = *reinterpret_cast<const x8*>(xr[mb] + 32 * u);
       if constexpr (NORM) gv[u] = *reinterpret_cast<const x8*>(gr + 32 * u);
     }
+  }
+  // W8: wave 0 fetches the block's row scales here, with the stream's first loads
+  EpiPre<T, EPI> pre{};
+  if constexpr (W8) {
+    if (wave == 0) pre.sc = epi_scale<EPI>(p, blockIdx.x, -1, lane);
   }
 
   float rs[MB];  // rstd of X rows r + 16 mb (NORM)
@@ -304,15 +386,24 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) 
   auto block = [&](int blk, auto refill_c) {
     constexpr bool REFILL = decltype(refill_c)::value;
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
+    for (int u = 0; u < US; ++u) {
 #pragma unroll
-      for (int mb = 0; mb < MB; ++mb) acc[mb] = mfma16x16x32<T>(a[u], bop(xv[mb][u], gv[u], mb), acc[mb]);
+      for (int h = 0; h < SPU; ++h) {
+        const x8 af = afrag(a[u], h);
+#pragma unroll
+        for (int mb = 0; mb < MB; ++mb)
+          acc[mb] = mfma16x16x32<T>(af, bop(xv[mb][SPU * u + h], gv[SPU * u + h], mb), acc[mb]);
+      }
       if constexpr (REFILL) {
-        const int s = (blk + 1) * U + u;
-        a[u] = __builtin_nontemporal_load(reinterpret_cast<const x8*>(wr + WS * s));
+        const int s = (blk + 1) * U + SPU * u;
+        a[u] = wload(s);
 #pragma unroll
-        for (int mb = 0; mb < MB; ++mb) xv[mb][u] = *reinterpret_cast<const x8*>(xr[mb] + 32 * s);
-        if constexpr (NORM) gv[u] = *reinterpret_cast<const x8*>(gr + 32 * s);
+        for (int h = 0; h < SPU; ++h) {
+#pragma unroll
+          for (int mb = 0; mb < MB; ++mb)
+            xv[mb][SPU * u + h] = *reinterpret_cast<const x8*>(xr[mb] + 32 * (s + h));
+          if constexpr (NORM) gv[SPU * u + h] = *reinterpret_cast<const x8*>(gr + 32 * (s + h));
+        }
       }
       // keep {MFMA u, refill u} in program order: hipcc would otherwise
       // cluster the dependent MFMA chain and issue every refill after it,
@@ -323,23 +414,48 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) 
   for (int blk = 0; blk + 1 < nblk; ++blk) block(blk, std::true_type{});
   if (nblk > 0) block(nblk - 1, std::false_type{});
   // leftover steps (K / WAVES not a multiple of 32 U): loads first, then MFMAs
+  // (W8: up to U - 1 steps in US pieces; an odd last step is an 8-B piece)
   {
     const int s0 = nblk * U, left = steps - s0;
+    constexpr int UL = W8 ? US : U - 1;
 #pragma unroll
-    for (int u = 0; u < U - 1; ++u) {
-      if (u < left) {
-        a[u] = __builtin_nontemporal_load(reinterpret_cast<const x8*>(wr + WS * (s0 + u)));
+    for (int u = 0; u < UL; ++u) {
+      if (SPU * u < left) {
+        if constexpr (W8) {
+          if (SPU * u + 1 < left) {
+            a[u] = wload(s0 + SPU * u);
+          } else {
+            const i2 t = __builtin_nontemporal_load(
+                reinterpret_cast<const i2*>(w8 + 512 * (s0 + SPU * u) + 8 * lane));
+            a[u] = i4{t[0], t[1], 0, 0};
+          }
+        } else {
+          a[u] = wload(s0 + u);
+        }
 #pragma unroll
-        for (int mb = 0; mb < MB; ++mb) xv[mb][u] = *reinterpret_cast<const x8*>(xr[mb] + 32 * (s0 + u));
-        if constexpr (NORM) gv[u] = *reinterpret_cast<const x8*>(gr + 32 * (s0 + u));
+        for (int h = 0; h < SPU; ++h) {
+          if (SPU * u + h < left) {
+            const int s = s0 + SPU * u + h;
+#pragma unroll
+            for (int mb = 0; mb < MB; ++mb)
+              xv[mb][SPU * u + h] = *reinterpret_cast<const x8*>(xr[mb] + 32 * s);
+            if constexpr (NORM) gv[SPU * u + h] = *reinterpret_cast<const x8*>(gr + 32 * s);
+          }
+        }
       }
     }
 #pragma unroll
-    for (int u = 0; u < U - 1; ++u)
-      if (u < left) {
+    for (int u = 0; u < UL; ++u) {
 #pragma unroll
-        for (int mb = 0; mb < MB; ++mb) acc[mb] = mfma16x16x32<T>(a[u], bop(xv[mb][u], gv[u], mb), acc[mb]);
+      for (int h = 0; h < SPU; ++h) {
+        if (SPU * u + h < left) {
+          const x8 af = afrag(a[u], h);
+#pragma unroll
+          for (int mb = 0; mb < MB; ++mb)
+            acc[mb] = mfma16x16x32<T>(af, bop(xv[mb][SPU * u + h], gv[SPU * u + h], mb), acc[mb]);
+        }
       }
+    }
   }
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb) part[wave][mb][lane] = acc[mb];
@@ -350,7 +466,8 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) 
     f4 t = part[0][mb][lane];
 #pragma unroll
     for (int i = 1; i < WAVES; ++i) t += part[i][mb][lane];  // fixed order: deterministic
-    epilogue<T, EPI, ACT>(p, blockIdx.x, t, lane, -1, EpiPre<T, EPI>{}, false, 16 * mb);
+    if constexpr (W8) t = scale_tile(t, pre.sc);
+    epilogue<T, EPI, ACT>(p, blockIdx.x, t, lane, -1, pre, false, 16 * mb);
   }
 }
 
@@ -367,11 +484,18 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) 
 //     the next block's first U k-steps, so the stream never drains;
 //   * per block, the 8 partial tiles meet in a double-buffered LDS slot and
 //     wave 0 runs the epilogue while the other waves stream the next block.
-template <typename T, bool NORM, int EPI, int ACT, int STEPS, int U, bool PACKED, int MB>
+// W8 (e4m3 weights): a ring slot is one 16-B piece = SPU = 2 k-steps; U counts
+// k-steps in flight as before, held in U / 2 slots.
+template <typename T, bool NORM, int EPI, int ACT, int STEPS, int U, bool PACKED, int MB,
+          bool W8 = false>
 __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
   typedef typename fa::MT<T>::x8 x8;
+  typedef std::conditional_t<W8, i4, x8> wslot;
+  typedef std::conditional_t<W8, unsigned char, T> WT;  // W8: the stream is addressed in bytes
   constexpr int WAVES = 8;
-  static_assert(STEPS % U == 0, "ring must tile the k-steps");
+  constexpr int SPU = W8 ? 2 : 1, US = U / SPU, SLOTS = STEPS / SPU;
+  static_assert(!W8 || PACKED, "e4m3 weights come decode-packed only");
+  static_assert(STEPS % U == 0 && U % SPU == 0, "ring must tile the k-steps");
   static_assert(!NORM || STEPS == 16, "the normed forms keep 64 gamma chunks per wave");
   static_assert(MB == 1 || STEPS == 16, "two row blocks keep 2 x 16 X fragments in registers");
   __shared__ f4 part[2][WAVES][MB][64];
@@ -380,7 +504,7 @@ __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int M = p.M, N = p.N, K = p.K;
   const T* __restrict__ x = (const T*)p.x;
-  const T* __restrict__ w = (const T*)p.w;
+  const WT* __restrict__ w = (const WT*)p.w;
   const int kbeg = wave * STEPS * 32;
   const int r = lane & 15, kc = 8 * (lane >> 4);
   bool xon[MB];
@@ -403,20 +527,33 @@ __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
   const int nunits = halves ? rounds + (wg < 2 * nrem ? 1 : 0) : (nblocks - wg + G - 1) / G;
   auto unit_blk = [&](int j) { return j < rounds || !halves ? wg + j * G : nblocks - nrem + wg / 2; };
   auto unit_half = [&](int j) { return j < rounds || !halves ? -1 : (wg & 1); };
-  // elements between a lane's consecutive k-steps of unit j
-  auto wstr = [&](int j) { return !PACKED ? 32 : unit_half(j) < 0 ? 512 : 256; };
+  // elements between a lane's consecutive k-steps of unit j (W8: bytes
+  // between its consecutive 16-B pieces: a 1 KiB / 512 B unit per two k-steps)
+  auto wstr = [&](int j) { return !PACKED ? 32 : unit_half(j) < 0 ? 512 * SPU : 256 * SPU; };
   auto wptr = [&](int j) {
     const int b = unit_blk(j), h = unit_half(j);
-    if constexpr (PACKED) {
+    if constexpr (W8) {
+      // the same (block, wave) / (half unit, wave) order as the 16-bit pack at
+      // 1 B per weight; lane L's piece at byte 16 L, in a half unit at 16 (kc + pr)
+      if (h < 0) return w + ((int64_t)b * WAVES + wave) * STEPS * 512 + 16 * lane;
+      const int64_t tail = (int64_t)(nblocks - nrem) * 16 * K;
+      const int unit = (b - (nblocks - nrem)) * 2 + h, pr = (r & 3) + 4 * (r >> 3);
+      return w + tail + ((int64_t)unit * WAVES + wave) * STEPS * 256 + 16 * (kc + pr);
+    } else if constexpr (PACKED) {
       if (h < 0) return w + ((int64_t)b * WAVES + wave) * STEPS * 512 + 8 * lane;
       const int64_t tail = (int64_t)(nblocks - nrem) * 16 * K;  // full blocks first
       const int unit = (b - (nblocks - nrem)) * 2 + h, pr = (r & 3) + 4 * (r >> 3);
       return w + tail + ((int64_t)unit * WAVES + wave) * STEPS * 256 + 8 * (kc + pr);
+    } else {
+      int64_t row;
+      if (h < 0) row = w_row<EPI>(b, r, N);
+      else row = (r < 8 ? 0 : (int64_t)N) + (int64_t)b * 8 + 4 * h + (r & 3);
+      return w + row * K + kbeg + kc;
     }
-    int64_t row;
-    if (h < 0) row = w_row<EPI>(b, r, N);
-    else row = (r < 8 ? 0 : (int64_t)N) + (int64_t)b * 8 + 4 * h + (r & 3);
-    return w + row * K + kbeg + kc;
+  };
+  auto afrag = [&](const wslot& v, int h) -> x8 {  // A fragment of the slot's k-step h
+    if constexpr (W8) return fp8x8<T>(v[2 * h], v[2 * h + 1]);
+    else return v;
   };
   int j = 0, blk = unit_blk(0), half = unit_half(0);
   EpiPre<T, EPI> pre[MB];  // wave 0: the epilogue operands of the current block
@@ -425,11 +562,16 @@ __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
     for (int mb = 0; mb < MB; ++mb) {
       epi_init<T, EPI>(p, lane, pre[mb], 16 * mb);
       epi_prefetch<T, EPI>(p, blk, lane, pre[mb], 16 * mb);
+      if constexpr (W8) pre[mb].sc = epi_scale<EPI>(p, blk, half, lane);
     }
   }
-  const T* wr = wptr(0);
-  const T* wn = wptr(nunits > 1 ? 1 : 0);
-  int ws = wstr(0), wsn = wstr(nunits > 1 ? 1 : 0);
+  // W8: where no unit follows, the ring's refills past the unit's end read one
+  // 16-B line of the scales (every lane the same address, stride 0; never
+  // used) instead of fetching a unit's first pieces a second time
+  const WT* wdummy = (const WT*)p.w_scale;
+  const WT* wr = wptr(0);
+  const WT* wn = W8 && nunits <= 1 ? wdummy : wptr(nunits > 1 ? 1 : 0);
+  int ws = wstr(0), wsn = W8 && nunits <= 1 ? 0 : wstr(nunits > 1 ? 1 : 0);
 
   // X (and gamma) first, the weight ring right behind them: a wave's loads
   // return in order, so X lands first and the norm prologue runs while the
@@ -453,7 +595,7 @@ __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
   x8 gl{};
   if constexpr (NORM) gl = *reinterpret_cast<const x8*>((const T*)p.norm_w + kbeg + 8 * lane);
   __builtin_amdgcn_sched_barrier(0);
-  x8 a[U];
+  wslot a[US];
   // Two normed row blocks keep 2 x 16 X fragments and spill ~0.5 KB per lane
   // in this prologue whatever the order (ring after the norm spills least):
   // the decode layer normalises 17-32 rows with the rmsnorm kernel and calls
@@ -462,7 +604,7 @@ __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
   constexpr bool RING_FIRST = !(NORM && MB == 2);
   if constexpr (RING_FIRST) {
 #pragma unroll
-    for (int u = 0; u < U; ++u) a[u] = __builtin_nontemporal_load(reinterpret_cast<const x8*>(wr + ws * u));
+    for (int u = 0; u < US; ++u) a[u] = __builtin_nontemporal_load(reinterpret_cast<const wslot*>(wr + ws * u));
   }
   if constexpr (NORM) {
 #pragma unroll
@@ -504,7 +646,7 @@ __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
 
   if constexpr (!RING_FIRST) {
 #pragma unroll
-    for (int u = 0; u < U; ++u) a[u] = __builtin_nontemporal_load(reinterpret_cast<const x8*>(wr + ws * u));
+    for (int u = 0; u < US; ++u) a[u] = __builtin_nontemporal_load(reinterpret_cast<const wslot*>(wr + ws * u));
   }
 
   // one block's k-steps; LAST: the workgroup's final block, whose last U
@@ -513,18 +655,27 @@ __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
   struct Acc {
     f4 v[MB];
   };
+  // (W8 runs the refilling copy alone: beside a second copy hipcc hoists the
+  // e4m3 conversions of every slot above the branch between the two, which
+  // holds 64 more registers and drains the ring (vmcnt(0)) at the head of each
+  // unit, and refills under a run-time predicate make it count vmcnt down to 0
+  // within every unit.  After the last unit the refills read `wdummy`.)
   auto run_block = [&](auto last_c) {
     constexpr bool LAST = decltype(last_c)::value;
     Acc acc;
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) acc.v[mb] = f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int s = 0; s < STEPS; ++s) {
+    for (int s = 0; s < SLOTS; ++s) {
 #pragma unroll
-      for (int mb = 0; mb < MB; ++mb) acc.v[mb] = mfma16x16x32<T>(a[s % U], xs[mb][s], acc.v[mb]);
-      if (!LAST || s + U < STEPS) {
-        const T* src = s + U < STEPS ? wr + ws * (s + U) : wn + wsn * (s + U - STEPS);
-        a[s % U] = __builtin_nontemporal_load(reinterpret_cast<const x8*>(src));
+      for (int h = 0; h < SPU; ++h) {
+        const x8 af = afrag(a[s % US], h);
+#pragma unroll
+        for (int mb = 0; mb < MB; ++mb) acc.v[mb] = mfma16x16x32<T>(af, xs[mb][SPU * s + h], acc.v[mb]);
+      }
+      if (!LAST || s + US < SLOTS) {
+        const WT* src = s + US < SLOTS ? wr + ws * (s + US) : wn + wsn * (s + US - SLOTS);
+        a[s % US] = __builtin_nontemporal_load(reinterpret_cast<const wslot*>(src));
       }
       __builtin_amdgcn_sched_barrier(0);  // {MFMA s, refill s} in program order
     }
@@ -532,7 +683,9 @@ __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
   };
   for (;; ++j) {
     const bool last = j + 1 >= nunits;
-    const Acc acc = last ? run_block(std::true_type{}) : run_block(std::false_type{});
+    Acc acc;
+    if constexpr (W8) acc = run_block(std::false_type{});
+    else acc = last ? run_block(std::true_type{}) : run_block(std::false_type{});
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) part[j & 1][wave][mb][lane] = acc.v[mb];
     __syncthreads();
@@ -542,6 +695,7 @@ __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
         f4 t = part[j & 1][0][mb][lane];
 #pragma unroll
         for (int i = 1; i < WAVES; ++i) t += part[j & 1][i][mb][lane];  // fixed order
+        if constexpr (W8) t = scale_tile(t, pre[mb].sc);
         epilogue<T, EPI, ACT>(p, blk, t, lane, half, pre[mb], true, 16 * mb);
       }
     }
@@ -550,12 +704,15 @@ __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
     half = unit_half(j + 1);
     if (wave == 0) {  // lands during the block's k-loop
 #pragma unroll
-      for (int mb = 0; mb < MB; ++mb) epi_prefetch<T, EPI>(p, blk, lane, pre[mb], 16 * mb);
+      for (int mb = 0; mb < MB; ++mb) {
+        epi_prefetch<T, EPI>(p, blk, lane, pre[mb], 16 * mb);
+        if constexpr (W8) pre[mb].sc = epi_scale<EPI>(p, blk, half, lane);
+      }
     }
     wr = wn;
     ws = wsn;
-    wn = wptr(j + 2 < nunits ? j + 2 : nunits - 1);
-    wsn = wstr(j + 2 < nunits ? j + 2 : nunits - 1);
+    wn = W8 && j + 2 >= nunits ? wdummy : wptr(j + 2 < nunits ? j + 2 : nunits - 1);
+    wsn = W8 && j + 2 >= nunits ? 0 : wstr(j + 2 < nunits ? j + 2 : nunits - 1);
   }
 }
 
@@ -575,6 +732,29 @@ int num_cus() {
 template <typename T, int WAVES, int STEPS, bool NORM, int EPI, int ACT>
 void launch(const SkinnyArgs& p, hipStream_t s) {
   const int nblocks = EPI == EPI_GLU ? p.N / 8 : p.N / 16;
+  if constexpr (WAVES == 8) {
+    if (p.w_scale) {  // e4m3 weights: packed 8-wave forms only (checked by the host)
+      if constexpr (STEPS == 0) {
+        if (p.M > 16)
+          hipLaunchKernelGGL((skinny_gemm_k<T, 8, NORM, EPI, ACT, true, 2, true>), dim3((unsigned)nblocks),
+                             dim3(512), 0, s, p);
+        else
+          hipLaunchKernelGGL((skinny_gemm_k<T, 8, NORM, EPI, ACT, true, 1, true>), dim3((unsigned)nblocks),
+                             dim3(512), 0, s, p);
+      } else {
+        // 16 k-steps in flight = 8 pieces per wave: the register ring of the
+        // 8-deep 16-bit forms, the whole block of a K = 4096 stream
+        const int g = nblocks < num_cus() ? nblocks : num_cus();
+        if (STEPS == 16 && p.M > 16)
+          hipLaunchKernelGGL((skinny_pgemm_k<T, NORM, EPI, ACT, STEPS, 16, true, STEPS == 16 ? 2 : 1, true>),
+                             dim3((unsigned)g), dim3(512), 0, s, p);
+        else
+          hipLaunchKernelGGL((skinny_pgemm_k<T, NORM, EPI, ACT, STEPS, 16, true, 1, true>),
+                             dim3((unsigned)g), dim3(512), 0, s, p);
+      }
+      return;
+    }
+  }
   if constexpr (STEPS == 0) {
     if (p.M > 16) {  // 17-32 rows: two row blocks per W fragment
       if constexpr (WAVES == 8) {

@@ -37,7 +37,7 @@ from ..ops._ext import use_native, ext
 from ..parallel.context import chunk_position_ids, ring_attention
 from ..ops.attention import flash_attn_qkvpacked, flash_attn_func, flash_decode_cached
 from ..ops.activations import glu, bias_gelu, gelu
-from ..ops import decode_pack
+from ..ops import decode_pack, fp8_weights
 from ..ops.softmax import FusedScaleMaskSoftmax
 from .enums import AttnMaskType, AttnType, LayerType, ModelType, PositionEmbeddingType
 from .module import MegatronModule
@@ -50,6 +50,17 @@ from .utils import attention_mask_func, erf_gelu
 # decode attention -> [dense + residual] -> [RMSNorm + fc1 + GLU] ->
 # [fc2 + residual].  EMA_DECODE_FUSED=0 keeps the unfused kernels.
 _DECODE_FUSED = os.environ.get("EMA_DECODE_FUSED", "1") != "0"
+# FP8 weight-only decode (--inference_fp8_weights, opt-in): the fused decode
+# layer streams its four products' weights as per-row-scaled e4m3
+# (ops/fp8_weights.py) wherever the shape packs; the LM head, the prefill and
+# the 16-bit parameters are untouched.
+_FP8_WEIGHTS = os.environ.get("EMA_FP8_WEIGHTS", "0") == "1"
+
+
+def set_fp8_weights(on):
+    """Switch FP8 weight-only decode for every fused decode layer of the process."""
+    global _FP8_WEIGHTS
+    _FP8_WEIGHTS = bool(on)
 
 
 def _linear_kwargs(args):
@@ -543,16 +554,24 @@ class ParallelTransformerLayer(MegatronModule):
         # the un-normed two-row-block forms (the normed ones spill their 2 x 16
         # X fragments: profiles/r4ai_skinny_mb.txt)
         sep = b > 16
-        pq, po = decode_pack.packed(wq), decode_pack.packed(wo)
         # the half-unit tail of the form that will run (normed for <= 16 rows)
         tail = C.skinny_glu_half_tail(w1.shape[0] // 2, w1.shape[1], not sep, b)
-        p1, p2 = decode_pack.packed(w1, glu=True, half_tail=tail), decode_pack.packed(w2)
+
+        def stream(w, **form):
+            """(weight to stream, its e4m3 row scales or None): the FP8 pair
+            under --inference_fp8_weights where the shape packs (each TP rank
+            quantises its own shard; a row-parallel partial sum is scaled
+            before the all-reduce), else the 16-bit pack or None."""
+            pair = fp8_weights.packed_fp8(w, **form) if _FP8_WEIGHTS else None
+            return pair if pair is not None else (decode_pack.packed(w, **form), None)
+        (pq, sq), (po, so) = stream(wq), stream(wo)
+        (p1, s1), (p2, s2) = stream(w1, glu=True, half_tail=tail), stream(w2)
         xq = rms_norm(x, ln1.weight, ln1.eps) if sep else x
         q = C.skinny_qkv_rope_cache(xq, wq if pq is None else pq, None if sep else ln1.weight,
                                     ln1.eps, ng, r, hd,
                                     cos, sin, pos, kc, vc,
                                     ip.device_offset if graph else None, 0 if graph else s0,
-                                    pq is not None)
+                                    pq is not None, sq)
         q4 = q.view(b, 1, ng * r, hd)
         if graph:
             o = flash_decode_cached(q4, kc.transpose(0, 1), vc.transpose(0, 1), ip.device_kv_len,
@@ -569,13 +588,13 @@ class ParallelTransformerLayer(MegatronModule):
         # measured 2.6x slower than the three launches: profiles/r3x_decode_mlp_fused.txt)
         first = state.get_tensor_model_parallel_rank() == 0
         h2 = C.skinny_norm_gemm(o.reshape(b, -1), wo if po is None else po, None, 0.0,
-                                x if first else None, po is not None)
+                                x if first else None, po is not None, so)
         h2 = tp.reduce_from_tensor_model_parallel_region(h2)
         y = C.skinny_norm_glu(rms_norm(h2, ln2.weight, ln2.eps) if sep else h2,
                               w1 if p1 is None else p1, None if sep else ln2.weight, ln2.eps,
-                              tp.layers._GLU_KIND[mlp.glu_activation], p1 is not None, tail)
+                              tp.layers._GLU_KIND[mlp.glu_activation], p1 is not None, tail, s1)
         h3 = C.skinny_norm_gemm(y, w2 if p2 is None else p2, None, 0.0, h2 if first else None,
-                                p2 is not None)
+                                p2 is not None, s2)
         h3 = tp.reduce_from_tensor_model_parallel_region(h3)
         return h3.view(1, b, H)
 
@@ -683,6 +702,8 @@ class ParallelTransformer(MegatronModule):
                  self_attn_mask_type=AttnMaskType.padding, pre_process=True, post_process=True,
                  drop_path_rate=0.0, args=None, model_type=None):
         super().__init__()
+        if getattr(args, "inference_fp8_weights", False):
+            set_fp8_weights(True)
         world_size = state.get_tensor_model_parallel_world_size()
         self.layer_type = layer_type
         self.model_type = model_type

@@ -38,6 +38,8 @@ def main():
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--eager_sample", action="store_true",
                     help="without --graph: sample with inference/sampling.py's eager chain")
+    ap.add_argument("--fp8_weights", action="store_true",
+                    help="FP8 weight-only decode (--inference_fp8_weights; ops/fp8_weights.py)")
     a = ap.parse_args()
     sampling = a.top_k > 0 or a.top_p > 0.0 or a.temperature != 1.0
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=os.environ.get("MASTER_PORT", "29561"),
@@ -69,6 +71,8 @@ def main():
             "--tokenizer_type", "NullTokenizer", "--synthetic_vocab_size", "32000",
             "--make_vocab_size_divisible_by", "128", "--micro_batch_size", "1",
             "--global_batch_size", "1", "--train_iters", "1", "--lr", "1e-4"]
+    if a.fp8_weights:
+        argv.append("--inference_fp8_weights")
     initialize_megatron(finetune.extra_args, {"tokenizer_type": "NullTokenizer"}, args_list=argv)
     model = get_model(finetune.model_provider, ModelType.encoder_or_decoder, wrap_with_ddp=False)
     m = model[0].eval()
