@@ -23,7 +23,27 @@
 // Numerics equal the unfused path's: the fp32 accumulator is rounded to the
 // operand dtype once, and the GLU math runs in fp32 on those rounded values.
 //
-// Structure (the 256x256 ping-pong of gemm_wgrad.hip, K-contiguous operands):
+// Three kernels, all on 256 (m) x 256 (n) output tiles in an XCD-aware grouped
+// tile order (an XCD's concurrent workgroups share A and B panels in its L2):
+//   * gemm_nt6_k, the product: persistent (one workgroup per CU), 4 waves of
+//     128 x 128 with AGPR-pinned accumulators, K in steps of 64 through a
+//     2-slot LDS-DMA ring, the K-steps of consecutive tiles one stream (the
+//     K-step executor of gemm_plan.h, shared with gemm_wgrad.hip's wgrad4_k),
+//     epilogues straight from registers, split-K for few-tile products.  It
+//     takes every production shape.
+//   * gemm_nt5_k, the one-shot 4-wave fallback (one tile per workgroup, same
+//     LDS layout, epilogue through LDS).  launch_one sends it what the
+//     persistent kernel does not take: fewer than two K-steps of 64, row-map
+//     groups that are not whole 256-row tiles, the GeGLU backward (its
+//     epilogue would spill the accumulators), an operand extent (the rows one
+//     descriptor spans) of 2^31 bytes or more.
+//   * gemm_nt_k, the 8-wave ping-pong fallback for what neither takes:
+//     K % 64 != 0 (K % 32 == 0 is the kernel's own limit), or operands past
+//     32-bit per-lane byte offsets (2^32).
+// EMA_GEMM_NT / gemm_nt_set_variant force 5 or 8 for A/B and tests.
+//
+// Structure of the 8-wave kernel (the 256x256 ping-pong of gemm_wgrad.hip,
+// K-contiguous operands; the 4-wave layout is described at its section below):
 //   * 256 (m) x 256 (n) output tile per workgroup, 8 waves as 2 (m) x 4 (n),
 //     each wave 128 x 64 = 8 x 4 tiles of v_mfma_f32_16x16x32, the operands
 //     passed as (B-frag, A-frag) so each lane's accumulator holds 4
@@ -63,8 +83,6 @@ namespace ema {
 namespace {
 
 using fa::static_for;
-
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 constexpr int TM = 256;               // output rows (m) per tile
 constexpr int TN = 256;               // output cols (n) per tile
@@ -134,7 +152,7 @@ __device__ __forceinline__ int64_t map_row(int64_t q, const RowMap& m) {
 }
 
 
-// ---- epilogue (both kernels) ------------------------------------------------
+// ---- epilogue through LDS (the two one-shot kernels) -------------------------
 // A wave's 128 x WNC output tile, rounded to 16 bits, sits in LDS as
 // [128 rows][WNC cols] with 16-B unit u of row r stored at unit u ^ (r & (U-1))
 // (U = WNC / 8 units per row).  The accumulator of fragment (i, j) holds row
@@ -384,30 +402,20 @@ __global__ void __launch_bounds__(512, 1) gemm_nt_k(NtArgs p) {
 }
 
 
-// ---- 4-wave variant: one wave per SIMD, 128 x 128 per wave, K in steps of 64 --
+// ---- 4-wave layout (gemm_nt5_k, gemm_nt6_k): one wave per SIMD, 128 x 128 per
+// wave, K in steps of 64 ------------------------------------------------------
 // 64 accumulator tiles (256 fp32 per lane) pinned in AGPRs by asm MFMAs; the
 // MFMA pipe is fed by the wave's own software pipeline instead of a partner
-// wave.  A K-step of 64 is two MFMA k-halves; while the 64 MFMAs of one half
-// run, the wave reads the next half's 16 fragments into the other register
-// set (one ds_read_b128 per 4 MFMAs) and, in the second half, issues the DMA
-// of step t+2 (one 1-KiB glds per 4 MFMAs).  Every DMA row is 128 B (a whole
-// cache line; the 32-deep 8-wave form fetches half lines, twice the L2
-// requests per byte), and half the fragment bytes per MFMA of the 8-wave
-// form.  LDS: 2 slots x (A + B) x [256 rows][64 k] = 128 KiB, 16-B chunk c of
-// row r at 16 (c ^ ((r >> 1) & 7)) (conflict-free fragment reads for both
-// k-halves); one barrier per K-step.
+// wave.  A K-step of 64 is two MFMA k-halves over two register fragment sets:
+// while one set's 64 MFMAs run, the wave reads the other set's 16 fragments
+// and issues the DMA of step t+2.  Every DMA row is 128 B (a whole cache line;
+// the 32-deep 8-wave form fetches half lines, twice the L2 requests per byte),
+// and half the fragment bytes per MFMA of the 8-wave form.  LDS: 2 slots x
+// (A + B) x [256 rows][64 k] = 128 KiB, 16-B chunk c of row r at
+// 16 (c ^ ((r >> 1) & 7)) (conflict-free fragment reads for both k-halves).
 constexpr int BK2 = 64;                     // K per step
 constexpr int OPB2 = 256 * BK2 * 2;         // 32 KiB per operand per step
 constexpr int SLOTB2 = 2 * OPB2;            // 64 KiB
-
-template <typename T>
-__device__ __forceinline__ void mfma_acc(f32x4& acc, typename fa::MT<T>::x8 a,
-                                         typename fa::MT<T>::x8 b) {
-  if constexpr (__is_same(T, bf16))
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-  else
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-}
 
 template <typename T>
 __device__ __forceinline__ void mfma_zero(f32x4& acc, typename fa::MT<T>::x8 z) {
@@ -417,8 +425,25 @@ __device__ __forceinline__ void mfma_zero(f32x4& acc, typename fa::MT<T>::x8 z) 
     asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_f16 %0, %1, %1, 0" : "=a"(acc) : "v"(z));
 }
 
+using K0 = std::integral_constant<int, 0>;  // k-half tags of read_frag
+using K1 = std::integral_constant<int, 1>;
+
+// ---- one-shot 4-wave kernel, early-refill schedule (variant 5) -------------
+// One tile per workgroup.  Each operand's half of a ring slot is refilled as
+// soon as every wave has read it, and the wait for the next K-step sits three
+// quarters into the current one, so a DMA piece has 1.0-1.5 K-steps to land.
+// One K-step = 32 groups of 4 MFMAs; after group G:
+//   G 0-3   read 2 A fragments of (t, k-half 1) -> set1
+//   G 5     lgkmcnt(0), BARRIER 1   (A of slot t read by every wave)
+//   G 6-13  DMA one A piece of step t+2 -> slot t
+//   G 6-9   read 2 B fragments of (t, k-half 1) -> set1
+//   G 11    lgkmcnt(0), BARRIER 2   (B of slot t read by every wave)
+//   G 12-19 DMA one B piece of step t+2 -> slot t
+//   G 23    vmcnt(16), BARRIER 3    (step t+1 landed, own DMA then everyone's)
+//   G 24-31 read 2 fragments of (t+1, k-half 0) -> set0 from slot t+1
+// then lgkmcnt(0).  Groups 0-15 run on set0 (k-half 0), 16-31 on set1.
 template <typename T, int EPI, int ACT>
-__global__ void __launch_bounds__(256, 1) gemm_nt4_k(NtArgs p) {
+__global__ void __launch_bounds__(256, 1) gemm_nt5_k(NtArgs p) {
   __shared__ __attribute__((aligned(1024))) char lds[2 * SLOTB2];
   typedef typename fa::MT<T>::x8 X8;
   const int lane = threadIdx.x & 63;
@@ -488,8 +513,6 @@ __global__ void __launch_bounds__(256, 1) gemm_nt4_k(NtArgs p) {
     if constexpr (F < 8) dst[F] = row_read_imm<2048 * F, T>(abase[KH] + so);
     else dst[F] = row_read_imm<2048 * (F - 8), T>(bbase[KH] + so);
   };
-  using K0 = std::integral_constant<int, 0>;
-  using K1 = std::integral_constant<int, 1>;
   auto mfma4 = [&](X8 (&cur)[16], auto g) {
     constexpr int G = decltype(g)::value;
     static_for<4>([&](auto q) {
@@ -516,153 +539,11 @@ __global__ void __launch_bounds__(256, 1) gemm_nt4_k(NtArgs p) {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_sched_barrier(0);
 
-  // K-step t (slot t & 1):
-  //   half 0: MFMAs on set0 = (t, 0); read (t, 1) -> set1 from slot t
-  //           vmcnt(0): step t+1 landed (own DMA, issued in half (t-1, 1))
-  //           lgkmcnt(0); BARRIER
-  //   half 1: MFMAs on set1; read (t+1, 0) -> set0 from slot t+1;
-  //           DMA of step t+2 -> slot t (clamped to the last step past the end)
-  //           lgkmcnt(0)
-  // RAW: step t+1 is retired by every wave before the barrier, and read only
-  //      after it.  WAR: slot t's last reads ((t, 1)) are retired before the
-  //      barrier, the DMA into it is issued after.
-  for (int t = 0; t < nt; ++t) {
-    const uint32_t so = (uint32_t)((t & 1) * SLOTB2), sn = (uint32_t)(SLOTB2 - so);
-    static_for<16>([&](auto g) {
-      mfma4(set0, g);
-      read_frag(set1, g, K1{}, so);
-      __builtin_amdgcn_sched_barrier(0);
-    });
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    const int ts = min(t + 2, nt - 1), slot = t & 1;
-    static_for<16>([&](auto g) {
-      mfma4(set1, g);
-      read_frag(set0, g, K0{}, sn);
-      stage_piece(decltype(g)::value, ts, slot);
-      __builtin_amdgcn_sched_barrier(0);
-    });
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the trailing re-fetches
-  __builtin_amdgcn_s_barrier();
-  fa::mfma_drain();  // VALU reads of the asm MFMAs' results
-
-  // epilogue: no ring read or DMA is pending
-  char* reg = lds + wave * 32768;
-  acc_to_lds<T, 8>(acc, reg, lane);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  epilogue_rows<T, EPI, ACT, 128>(p, reg, lane, m0 + 128 * wm,
-                                  n0 + (EPI == EPI_GLU ? 64 : 128) * wn);
-}
-
-// ---- 4-wave variant, early-refill schedule (variant 5) ---------------------
-// Same tile, LDS image and fragment sets as gemm_nt4_k, but each operand's
-// half of a ring slot is refilled as soon as every wave has read it, and the
-// wait for the next K-step sits three quarters into the current one, so a
-// DMA piece has 1.0-1.5 K-steps (not 0.5-1.0) to land.  One K-step = 32
-// groups of 4 MFMAs; after group G:
-//   G 0-3   read 2 A fragments of (t, k-half 1) -> set1
-//   G 5     lgkmcnt(0), BARRIER 1   (A of slot t read by every wave)
-//   G 6-13  DMA one A piece of step t+2 -> slot t
-//   G 6-9   read 2 B fragments of (t, k-half 1) -> set1
-//   G 11    lgkmcnt(0), BARRIER 2   (B of slot t read by every wave)
-//   G 12-19 DMA one B piece of step t+2 -> slot t
-//   G 23    vmcnt(16), BARRIER 3    (step t+1 landed, own DMA then everyone's)
-//   G 24-31 read 2 fragments of (t+1, k-half 0) -> set0 from slot t+1
-// then lgkmcnt(0).  Groups 0-15 run on set0 (k-half 0), 16-31 on set1.
-template <typename T, int EPI, int ACT>
-__global__ void __launch_bounds__(256, 1) gemm_nt5_k(NtArgs p) {
-  __shared__ __attribute__((aligned(1024))) char lds[2 * SLOTB2];
-  typedef typename fa::MT<T>::x8 X8;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int wm = wave >> 1, wn = wave & 1;
-
-  const int ntiles = p.ntm * p.ntn;
-  const int lin = xcd_remap((int)blockIdx.x, ntiles);
-  const int2 tt = tile_of(lin, p.ntm, p.ntn, p.gm);
-  const int64_t m0 = (int64_t)tt.x * TM;
-  const int64_t n0 = (int64_t)tt.y * (EPI == EPI_GLU ? TN / 2 : TN);
-  const int M = p.M, N = p.N;
-
-  uint32_t off[16];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int tr = 8 * (8 * wave + i) + (lane >> 3);
-    const int c = (lane & 7) ^ ((tr >> 1) & 7);
-    int64_t am = m0 + tr;
-    am = map_row(am < M ? am : M - 1, p.am);
-    off[i] = (uint32_t)((am * p.lda + 8 * c) * (int64_t)sizeof(T));
-    int64_t bn;
-    if constexpr (EPI == EPI_GLU) {
-      const int band = tr >> 7, q = tr & 127;
-      const int64_t f = n0 + 64 * band + (q & 63);
-      bn = f < N ? (q < 64 ? f : N + f) : 0;
-    } else {
-      bn = n0 + tr;
-      bn = bn < N ? bn : N - 1;
-    }
-    off[8 + i] = (uint32_t)((bn * p.ldb + 8 * c) * (int64_t)sizeof(T));
-  }
-  const char* const abyte = reinterpret_cast<const char*>(p.a);
-  const char* const bbyte = reinterpret_cast<const char*>(p.b);
-  char* const ldsp = lds;
-  const int nt = p.K / BK2;
-  auto stage_piece = [&](int q, int ts, int slot) {
-    const char* base = (q < 8 ? abyte : bbyte) + (int64_t)ts * (BK2 * (int)sizeof(T));
-    const int dst = slot * SLOTB2 + (q >= 8 ? OPB2 : 0) + (8 * wave + (q & 7)) * 1024;
-    __builtin_amdgcn_global_load_lds((const void*)(base + off[q]),
-                                     (__attribute__((address_space(3))) void*)(ldsp + dst), 16, 0, 0);
-  };
-
-  f32x4 acc[8][8];
-  const uint32_t lds_base = (uint32_t)(uintptr_t)lds;
-  const int fr = lane & 15, fsw = (fr >> 1) & 7;
-  uint32_t abase[2], bbase[2];
-#pragma unroll
-  for (int kh = 0; kh < 2; ++kh) {
-    const uint32_t ch = 16u * (uint32_t)(((lane >> 4) + 4 * kh) ^ fsw);
-    abase[kh] = lds_base + 128u * (128u * wm + fr) + ch;
-    bbase[kh] = lds_base + OPB2 + 128u * (128u * wn + fr) + ch;
-  }
-  X8 set0[16], set1[16];
-  auto read_frag = [&](X8 (&dst)[16], auto f, auto kh, uint32_t so) {
-    constexpr int F = decltype(f)::value, KH = decltype(kh)::value;
-    if constexpr (F < 8) dst[F] = row_read_imm<2048 * F, T>(abase[KH] + so);
-    else dst[F] = row_read_imm<2048 * (F - 8), T>(bbase[KH] + so);
-  };
-  using K0 = std::integral_constant<int, 0>;
-  using K1 = std::integral_constant<int, 1>;
-  auto mfma4 = [&](X8 (&cur)[16], auto g) {
-    constexpr int G = decltype(g)::value;
-    static_for<4>([&](auto q) {
-      constexpr int IDX = 4 * G + decltype(q)::value, I = IDX / 8, J = IDX % 8;
-      mfma_acc<T>(acc[I][J], cur[8 + J], cur[I]);
-    });
-  };
-
-  static_for<16>([&](auto q) { stage_piece(decltype(q)::value, 0, 0); });
-  static_for<16>([&](auto q) { stage_piece(decltype(q)::value, min(1, nt - 1), 1); });
-  {
-    X8 z;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) z[e] = (T)0.f;
-    static_for<64>([&](auto q) {
-      constexpr int I = decltype(q)::value / 8, J = decltype(q)::value % 8;
-      mfma_zero<T>(acc[I][J], z);
-    });
-  }
-  asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  static_for<16>([&](auto f) { read_frag(set0, f, K0{}, 0u); });
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-
+  // K-step t uses slot t & 1; the DMA of step t+2 is clamped to the last step
+  // past the end (the trailing re-fetches).
+  // RAW: step t+1 is retired by every wave before BARRIER 3, and read only
+  //      after it.  WAR: an operand's half of slot t is last read (k-half 1)
+  //      before its barrier (1: A, 2: B), the DMA into it is issued after.
   for (int t = 0; t < nt; ++t) {
     const uint32_t so = (uint32_t)((t & 1) * SLOTB2), sn = (uint32_t)(SLOTB2 - so);
     const int ts = min(t + 2, nt - 1), slot = t & 1;
@@ -699,10 +580,11 @@ __global__ void __launch_bounds__(256, 1) gemm_nt5_k(NtArgs p) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the trailing re-fetches
   __builtin_amdgcn_s_barrier();
-  fa::mfma_drain();
+  fa::mfma_drain();  // VALU reads of the asm MFMAs' results
 
+  // epilogue: no ring read or DMA is pending
   char* reg = lds + wave * 32768;
   acc_to_lds<T, 8>(acc, reg, lane);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -710,34 +592,24 @@ __global__ void __launch_bounds__(256, 1) gemm_nt5_k(NtArgs p) {
                                   n0 + (EPI == EPI_GLU ? 64 : 128) * wn);
 }
 
-// ---- persistent 4-wave variant (variant 6, EPI_STORE without row maps) ------
-// The early-refill K-step of gemm_nt5_k, run as one continuous stream of
-// K-steps over all the tiles a workgroup owns (grid = one workgroup per CU,
-// tiles dealt round-robin in XCD-grouped order).  The DMA of the next tile's
-// first two K-steps rides in the current tile's last two K-steps, so a tile
-// starts with its operands already in LDS; the epilogue goes from registers
+// ---- persistent 4-wave kernel (variant 6): every epilogue, row maps, split-K -
+// The early-refill K-step (gemm_plan.h, shared with gemm_wgrad.hip's
+// wgrad4_k), run as one continuous stream of K-steps over all the tiles a
+// workgroup owns (grid = one workgroup per CU, tiles dealt round-robin in
+// XCD-grouped order).  The DMA of the next tile's first two K-steps rides in
+// the current tile's last two K-steps, so a tile starts with its operands
+// already in LDS; the epilogue goes from registers
 // straight to global memory (bf16 pack + two permlane swaps give each lane 8
 // consecutive columns, one 16-B store per fragment pair), leaving the LDS ring
 // to the next tile's data; the first k-half of a tile accumulates onto C = 0.
 // Operands are read by buffer_load ... lds through a per-tile descriptor whose
 // size ends at the last valid row: rows past M / N read as zeros (no clamping).
 template <typename T>
-__device__ __forceinline__ void mfma_acc0(f32x4& acc, typename fa::MT<T>::x8 a,
-                                          typename fa::MT<T>::x8 b) {
-  if constexpr (__is_same(T, bf16))
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=a"(acc) : "v"(a), "v"(b));
-  else
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=a"(acc) : "v"(a), "v"(b));
-}
-
-template <typename T>
 __device__ __forceinline__ uint2 pack4(f32x4 v) {
   typename fa::MT<T>::x4 h;
   h[0] = (T)v[0]; h[1] = (T)v[1]; h[2] = (T)v[2]; h[3] = (T)v[3];
   return *reinterpret_cast<uint2*>(&h);
 }
-
-typedef __amdgpu_buffer_rsrc_t Rsrc;
 
 // Two accumulator fragments (cols 16 j + 4 q' and 16 (j+1) + 4 q' of one row on
 // lane group q' = lane >> 4), packed to 16 bits, become 8 CONSECUTIVE columns
@@ -946,8 +818,6 @@ __global__ void __launch_bounds__(256, 1) gemm_nt6_k(NtArgs p) {
     if constexpr (F < 8) dst[F] = row_read_imm<2048 * F, T>(abase[KH] + so);
     else dst[F] = row_read_imm<2048 * (F - 8), T>(bbase[KH] + so);
   };
-  using K0 = std::integral_constant<int, 0>;
-  using K1 = std::integral_constant<int, 1>;
 
   Rsrc ra_c, rb_c, ra_n, rb_n;  // current / next tile
   make_rsrc(0, ra_c, rb_c);
@@ -971,37 +841,10 @@ __global__ void __launch_bounds__(256, 1) gemm_nt6_k(NtArgs p) {
       const bool here = t + 2 < nt;
       const Rsrc ra = here ? ra_c : ra_n, rb = here ? rb_c : rb_n;
       const uint32_t soff = (uint32_t)((here ? t + 2 : t + 2 - nt) * BK2 * (int)sizeof(T));
-      // One-MFMA slot plan (kNtPlan: events after MFMA index S; +1-5 % over
-      // the round-4 plan, profiles/r5e_gemm_lab.txt)
-      constexpr int VMW = nt_plan_vmw();
-      static_for<128>([&](auto sc) {
-        constexpr int S = decltype(sc)::value, IDX = S & 63, I = IDX / 8, J = IDX % 8;
-        if constexpr (S < 64) {
-          if constexpr (decltype(zero)::value) mfma_acc0<T>(acc[I][J], set0[8 + J], set0[I]);
-          else mfma_acc<T>(acc[I][J], set0[8 + J], set0[I]);
-        } else {
-          mfma_acc<T>(acc[I][J], set1[8 + J], set1[I]);
-        }
-        static_for<16>([&](auto ec) {
-          constexpr int E = decltype(ec)::value;
-          if constexpr (kNtPlan.rd1[E] == S) read_frag(set1, std::integral_constant<int, E>{}, K1{}, so);
-          if constexpr (kNtPlan.dma[E] == S) dma(E, E < 8 ? ra : rb, soff, slot);
-          if constexpr (kNtPlan.rd0[E] == S) read_frag(set0, std::integral_constant<int, E>{}, K0{}, sn);
-        });
-        if constexpr (S == kNtPlan.b1 || S == kNtPlan.b2) {
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_sched_barrier(0);
-          __builtin_amdgcn_s_barrier();
-        }
-        if constexpr (S == kNtPlan.w) {
-          asm volatile("s_waitcnt vmcnt(%0)" ::"i"(VMW) : "memory");
-          __builtin_amdgcn_sched_barrier(0);
-          __builtin_amdgcn_s_barrier();
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      });
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
+      nt_plan_kstep<T, decltype(zero)::value>(
+          acc, set0, set1, [&](auto e) { read_frag(set1, e, K1{}, so); },
+          [&](auto e) { dma(decltype(e)::value, decltype(e)::value < 8 ? ra : rb, soff, slot); },
+          [&](auto e) { read_frag(set0, e, K0{}, sn); });
     };
     kstep(0, std::true_type{});
     for (int t = 1; t < nt; ++t) kstep(t, std::false_type{});
@@ -1076,16 +919,13 @@ int nt_ksplit(int tiles, int64_t K) {
 // n-tiles when M has more tiles) on the 7B shapes, one box
 // (profiles/r6t_gemm_group_sweep.txt): fc1 + GLU +3.8 %, fc2 dgrad + dGLU
 // +2.7 %, plain products +0.5 %.  EMA_GEMM_GM=<g> overrides (> 0: groups of g
-// m-tiles, < 0: groups of -g n-tiles); EMA_GEMM_GM=old restores the old rule.
-int group_m(int ntm, int ntn) {
+// m-tiles, < 0: groups of -g n-tiles).
+int group_m() {
   static const int env = [] {
     const char* e = getenv("EMA_GEMM_GM");
-    if (e && e[0] == 'o') return 1 << 20;
     return e ? atoi(e) : 0;
   }();
-  if (env == 1 << 20) return ntm <= ntn ? 8 : -8;
-  if (env != 0) return env;
-  return 4;
+  return env != 0 ? env : 4;
 }
 
 #define EMA_GLU_KIND2(kind, ...)                              \
@@ -1096,9 +936,9 @@ int group_m(int ntm, int ntn) {
     default: { constexpr int A_ = 3; __VA_ARGS__; break; }    \
   }
 
-// Kernel variant per epilogue: 6 (persistent 4-wave, register epilogue; row
-// maps fall back to 5), 5 (one-shot early-refill 4-wave), 4 (one-shot, one
-// refill point), 8 (8-wave ping-pong).  Defaults from interleaved same-box
+// Kernel variant per epilogue: 6 (persistent 4-wave, register epilogue), 5
+// (one-shot early-refill 4-wave), 8 (8-wave ping-pong); launch_one falls back
+// 6 -> 5 -> 8 where a shape does not fit.  Defaults from interleaved same-box
 // A/B on the 7B shapes (profiles/r5g_gemm_nt_bench.txt): 6 everywhere (fc1 +
 // GLU 1.04x hipBLASLt + glu kernel vs 1.02x on 5; fc2 dgrad + dGLU 1.13x vs
 // 1.05x; plain products 0.93-0.99x hipBLASLt, so those stay on hipBLASLt
@@ -1107,7 +947,7 @@ int group_m(int ntm, int ntn) {
 // (EMA_GEMM_NT_STORE=<v>: the plain / row-mapped products only)
 // (A/B in one process); gemm_nt_set_variant(0) restores the defaults.
 int g_var[3] = {6, 6, 6};  // [EPI_STORE, EPI_GLU, EPI_DGLU]
-int parse_variant(int v) { return (v == 4 || v == 5 || v == 6 || v == 8) ? v : 0; }
+int parse_variant(int v) { return (v == 5 || v == 6 || v == 8) ? v : 0; }
 const int g_env_variant = [] {
   const char* e = getenv("EMA_GEMM_NT");
   const int v = e ? parse_variant(atoi(e)) : 0;
@@ -1160,10 +1000,10 @@ void launch_one(const NtArgs& p, hipStream_t s) {
       return;
     }
   }
-  const bool w4 = g_var[EPI] != 8 && p.K % BK2 == 0 && p.wave4_ok;
-  if (w4 && g_var[EPI] != 4) hipLaunchKernelGGL((gemm_nt5_k<T, EPI, ACT>), grid, dim3(256), 0, s, p);
-  else if (w4) hipLaunchKernelGGL((gemm_nt4_k<T, EPI, ACT>), grid, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL((gemm_nt_k<T, EPI, ACT>), grid, dim3(512), 0, s, p);
+  if (g_var[EPI] != 8 && p.K % BK2 == 0 && p.wave4_ok)
+    hipLaunchKernelGGL((gemm_nt5_k<T, EPI, ACT>), grid, dim3(256), 0, s, p);
+  else
+    hipLaunchKernelGGL((gemm_nt_k<T, EPI, ACT>), grid, dim3(512), 0, s, p);
 }
 
 template <int EPI>
@@ -1171,7 +1011,7 @@ void launch_nt(NtArgs& p, int kind, int dt, hipStream_t s) {
   const int n_out = EPI == EPI_GLU ? (p.N + TN / 2 - 1) / (TN / 2) : (p.N + TN - 1) / TN;
   p.ntm = (p.M + TM - 1) / TM;
   p.ntn = n_out;
-  p.gm = group_m(p.ntm, p.ntn);
+  p.gm = group_m();
   const int64_t brows = EPI == EPI_GLU ? 2 * (int64_t)p.N : p.N;
   // highest A row read (through the remap: groups are increasing in q)
   const int64_t arows = p.am.rows == 0 ? p.M

@@ -61,8 +61,6 @@ namespace {
 
 using fa::static_for;
 
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
 constexpr int TN = 256;               // output rows (n) per tile
 constexpr int TK = 256;               // output cols (k) per tile
 constexpr int BM = 32;                // tokens per subtile = one MFMA k-step
@@ -377,26 +375,9 @@ wgrad_k(const T* __restrict__ dy, const T* __restrict__ x, float* __restrict__ g
 // column and ends at the end of the operand, so a piece is one per-lane VGPR
 // (wave parity variant) plus an SGPR offset (token row block + 128-B column
 // block), and the last rows of a ragged edge read zeros past the buffer end.
-typedef __attribute__((ext_vector_type(4))) float f32x4_;
-typedef __amdgpu_buffer_rsrc_t Rsrc;
 constexpr int IMG = 32 * 256 * 2;        // one [32][256] 16-bit image (a)
 constexpr int OPB2 = 2 * IMG;            // operand per K-step (64 tokens)
 constexpr int SLOTB2 = 2 * OPB2;         // dY + X
-
-template <typename T>
-__device__ __forceinline__ void wmfma(f32x4_& acc, typename fa::MT<T>::x8 a, typename fa::MT<T>::x8 b) {
-  if constexpr (__is_same(T, bf16))
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-  else
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
-}
-template <typename T>
-__device__ __forceinline__ void wmfma0(f32x4_& acc, typename fa::MT<T>::x8 a, typename fa::MT<T>::x8 b) {
-  if constexpr (__is_same(T, bf16))
-    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=a"(acc) : "v"(a), "v"(b));
-  else
-    asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=a"(acc) : "v"(a), "v"(b));
-}
 
 // Arguments of the persistent 4-wave kernel.  Items: whole tiles [0, nitems)
 // over all M tokens, or (SPLIT) token pieces of the tiles [lin0, lin0 + nlin):
@@ -499,7 +480,7 @@ __global__ void __launch_bounds__(256, 1) wgrad4_k(W4Args a) {
     }
   };
 
-  f32x4_ acc[8][8];
+  f32x4 acc[8][8];
   const uint32_t lds_base = (uint32_t)(uintptr_t)lds;
   uint32_t abase[2][2], bbase[2][2];
 #pragma unroll
@@ -548,37 +529,12 @@ __global__ void __launch_bounds__(256, 1) wgrad4_k(W4Args a) {
       const int s2 = here ? t + 2 : t + 2 - nt;
       uint32_t xr[2];
       xrows_of(here ? q_c : q_n, s2, xr);
-      // the shared slot plan (gemm_plan.h) with A = dY, B = X: dY's pieces of
+      // the shared K-step (gemm_plan.h) with A = dY, B = X: dY's pieces of
       // step t+2 after barrier 1, X's after barrier 2, 13 before the wait
-      constexpr int VMW = nt_plan_vmw();
-      static_for<128>([&](auto sc) {
-        constexpr int S = decltype(sc)::value, IDX = S & 63, I = IDX / 8, J = IDX % 8;
-        if constexpr (S < 64) {
-          if constexpr (decltype(zero)::value) wmfma0<T>(acc[I][J], set0[8 + J], set0[I]);
-          else wmfma<T>(acc[I][J], set0[8 + J], set0[I]);
-        } else {
-          wmfma<T>(acc[I][J], set1[8 + J], set1[I]);
-        }
-        static_for<16>([&](auto ec) {
-          constexpr int E = decltype(ec)::value;
-          if constexpr (kNtPlan.rd1[E] == S) read_frag(set1, std::integral_constant<int, E>{}, K1{}, so);
-          if constexpr (kNtPlan.dma[E] == S) dmaq(E, ra, rb, s2, slot, xr);
-          if constexpr (kNtPlan.rd0[E] == S) read_frag(set0, std::integral_constant<int, E>{}, K0{}, sn);
-        });
-        if constexpr (S == kNtPlan.b1 || S == kNtPlan.b2) {
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-          __builtin_amdgcn_sched_barrier(0);
-          __builtin_amdgcn_s_barrier();
-        }
-        if constexpr (S == kNtPlan.w) {
-          asm volatile("s_waitcnt vmcnt(%0)" ::"i"(VMW) : "memory");
-          __builtin_amdgcn_sched_barrier(0);
-          __builtin_amdgcn_s_barrier();
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      });
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_sched_barrier(0);
+      nt_plan_kstep<T, decltype(zero)::value>(
+          acc, set0, set1, [&](auto e) { read_frag(set1, e, K1{}, so); },
+          [&](auto e) { dmaq(decltype(e)::value, ra, rb, s2, slot, xr); },
+          [&](auto e) { read_frag(set0, e, K0{}, sn); });
     };
     kstep(0, std::true_type{});
     for (int t = 1; t < nt; ++t) kstep(t, std::false_type{});
@@ -596,22 +552,22 @@ __global__ void __launch_bounds__(256, 1) wgrad4_k(W4Args a) {
       for (int ii = 0; ii < 8; ++ii)
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-          __builtin_nontemporal_store(acc[ii][j], reinterpret_cast<f32x4_*>(wb + 16 * ii * TK + 16 * j));
+          __builtin_nontemporal_store(acc[ii][j], reinterpret_cast<f32x4*>(wb + 16 * ii * TK + 16 * j));
     } else {
       const int64_t kc = k0 + 128 * wk + 4 * (lane >> 4);
       const int64_t nr = n0 + 128 * wn + (lane & 15);
 #pragma unroll
       for (int ii = 0; ii < 8; ++ii) {
         const int64_t n = nr + 16 * ii;
-        f32x4_* row = reinterpret_cast<f32x4_*>(a.g + n * K + kc);
+        f32x4* row = reinterpret_cast<f32x4*>(a.g + n * K + kc);
         if constexpr (ACCUM) {
 #pragma unroll
           for (int jh = 0; jh < 8; jh += 4) {
-            f32x4_ o[4];
+            f32x4 o[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j)
               o[j] = (n < N && kc + 16 * (jh + j) < K) ? __builtin_nontemporal_load(row + 4 * (jh + j))
-                                                        : f32x4_{0, 0, 0, 0};
+                                                        : f32x4{0, 0, 0, 0};
 #pragma unroll
             for (int j = 0; j < 4; ++j)
               if (n < N && kc + 16 * (jh + j) < K)

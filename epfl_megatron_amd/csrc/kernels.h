@@ -294,7 +294,7 @@ struct TokMap {
 void wgrad_gemm(const void* dy, const void* x, float* g, int64_t M, int64_t N, int64_t K,
                 bool accumulate, int dt, hipStream_t s, float* ws = nullptr, TokMap xmap = {});
 // ---- gemm_nt.hip: C[M,N] = A[M,K] B[N,K]^T (forward / dgrad), GLU epilogues --
-void gemm_nt_set_variant(int v);  // 4 or 8 waves per workgroup
+void gemm_nt_set_variant(int v);  // 6 persistent, 5 one-shot 4-wave, 8 8-wave; else the defaults
 bool gemm_nt_supported(int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc);
 // Row-group remap of an operand's rows (the chunked TP all-gather / reduce-
 // scatter overlap): logical row q lives at physical row

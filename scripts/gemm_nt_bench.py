@@ -37,7 +37,7 @@ def main():
     ap.add_argument("--qkv", type=int, default=12288)
     ap.add_argument("--tp", type=int, default=1)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--variants", default="4,8", help="NT GEMM kernel variants to time")
+    ap.add_argument("--variants", default="6", help="NT GEMM kernel variants to time (5, 6, 8)")
     args = ap.parse_args()
     from epfl_megatron_amd.ops._ext import ext
     C = ext()

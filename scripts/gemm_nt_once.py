@@ -1,5 +1,5 @@
-"""Profiling driver: one NT GEMM shape through hipBLASLt and both hand-written
-variants (5 calls each), uniform-random bf16 operands.
+"""Profiling driver: one NT GEMM shape through hipBLASLt and the hand-written
+kernels (5 calls each), uniform-random bf16 operands.
 
     python scripts/gemm_nt_once.py [M N K]
 """
@@ -18,7 +18,7 @@ b = torch.empty(N, K, device="cuda", dtype=torch.bfloat16).uniform_(-1, 1)
 out = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
 for _ in range(5):
     torch.matmul(a, b.t(), out=out)
-for v in (8, 4):
+for v in (8, 5, 6):
     C.gemm_nt_set_variant(v)
     for _ in range(5):
         C.gemm_nt(a, b, out)
