@@ -58,6 +58,15 @@ FLAG_TABLE = {
                    "the bytes per decode step).  Activations, KV cache, LM head, prefill and "
                    "the 16-bit parameters are unchanged.  Changes the outputs by the weight "
                    "quantisation error: opt-in"),
+        _flag("--inference_fp8_kv_cache", action="store_true",
+              help="FP8 KV cache: K and V are cached as e4m3 bytes with an fp32 scale per KV "
+                   "head (ops/fp8_kv.py; half the cache memory and half the bytes decode "
+                   "attention streams per step).  Changes the outputs by one e4m3 rounding of "
+                   "each cached value: opt-in"),
+        _flag("--inference_fp8_kv_calibrate", action="store_true",
+              help="with --inference_fp8_kv_cache: the prefill that restarts a cache sets each "
+                   "head's scale from the prompt (2 amax / 448 rounded up to a power of two); "
+                   "later values saturate.  Without it the scales stay 1.0"),
         _flag("--inference_fused_sampling", action="store_true",
               help="sample the next token with one fused HIP launch (temperature, top-k or "
                    "top-p and a Gumbel-max draw from Philox noise; ops/sampling.py) instead of "

@@ -797,6 +797,61 @@ at::Tensor skinny_norm_glu(const at::Tensor& x, const at::Tensor& w1,
 }
 
 
+// FP8 KV cache scales: fp32 [2, nkv] (row 0: K, row 1: V) on x's device
+static const float* kv_scale_ptr(const at::Tensor& sc, int64_t nkv, const at::Tensor& x) {
+  TORCH_CHECK(sc.is_cuda() && sc.device() == x.device() && sc.scalar_type() == at::kFloat &&
+              sc.is_contiguous() && sc.dim() == 2 && sc.size(0) == 2 && sc.size(1) == nkv,
+              "FP8 KV cache: kv_scale must be a contiguous device fp32 tensor [2, nkv]");
+  return sc.data_ptr<float>();
+}
+
+// Quantising store of k / v [sq, b, nkv, hd] (bf16 / fp16, hd contiguous) into
+// rows slot .. slot + sq - 1 of the e4m3 caches [L, B, nkv, hd] (uint8 views at
+// the batch offset); slot from `slot_t` (int64 device scalar) when given.
+void kv_store_fp8(const at::Tensor& k, const at::Tensor& v, at::Tensor kcache, at::Tensor vcache,
+                  const at::Tensor& kv_scale, const c10::optional<at::Tensor>& slot_t,
+                  int64_t slot) {
+  check_gpu(k, "k");
+  TORCH_CHECK(k.scalar_type() == at::kBFloat16 || k.scalar_type() == at::kHalf,
+              "kv store: k / v must be bf16 or fp16");
+  TORCH_CHECK(v.is_cuda() && v.scalar_type() == k.scalar_type() && k.dim() == 4 &&
+              v.sizes() == k.sizes(), "kv store: k / v [sq, b, nkv, hd] of one dtype");
+  const int64_t sq = k.size(0), b = k.size(1), nkv = k.size(2), hd = k.size(3);
+  TORCH_CHECK(hd % 8 == 0, "kv store: head_dim must be a multiple of 8");
+  for (const at::Tensor* t : {&k, &v}) {
+    TORCH_CHECK(t->stride(3) == 1 && t->stride(0) % 8 == 0 && t->stride(1) % 8 == 0 &&
+                t->stride(2) % 8 == 0, "kv store: k / v strides must keep 16-byte alignment");
+    check_vec_aligned(*t, "k/v");
+  }
+  for (const at::Tensor* c : {&kcache, &vcache}) {
+    TORCH_CHECK(c->is_cuda() && c->device() == k.device() && c->scalar_type() == at::kByte &&
+                c->dim() == 4 && c->size(1) >= b && c->size(2) == nkv && c->size(3) == hd &&
+                c->stride(3) == 1 && c->stride(2) == hd && c->stride(1) % 8 == 0 &&
+                c->stride(0) % 8 == 0 && reinterpret_cast<uintptr_t>(c->data_ptr()) % 8 == 0,
+                "kv store: caches uint8 [L, B, nkv, hd] with packed heads");
+  }
+  TORCH_CHECK(kcache.size(0) == vcache.size(0) && kcache.stride(0) == vcache.stride(0) &&
+              kcache.stride(1) == vcache.stride(1), "kv store: k / v cache shapes differ");
+  ema::KvStoreParams p{};
+  p.scales = kv_scale_ptr(kv_scale, nkv, k);
+  if (slot_t) {
+    TORCH_CHECK(slot_t->is_cuda() && slot_t->scalar_type() == at::kLong && slot_t->numel() >= 1,
+                "kv store: slot int64");
+    TORCH_CHECK(sq <= kcache.size(0), "kv store: more rows than the cache holds");
+    p.slot_ptr = slot_t->data_ptr<int64_t>();
+  } else {
+    TORCH_CHECK(slot >= 0 && slot + sq <= kcache.size(0), "kv store: slot out of range");
+    p.slot = slot;
+  }
+  p.k = k.data_ptr(); p.v = v.data_ptr();
+  p.kcache = kcache.data_ptr<uint8_t>(); p.vcache = vcache.data_ptr<uint8_t>();
+  p.k_ss = k.stride(0); p.k_sb = k.stride(1); p.k_sg = k.stride(2);
+  p.v_ss = v.stride(0); p.v_sb = v.stride(1); p.v_sg = v.stride(2);
+  p.c_ss = kcache.stride(0); p.c_sb = kcache.stride(1);
+  p.sq = (int)sq; p.b = (int)b; p.nkv = (int)nkv; p.hd = (int)hd;
+  ema::kv_store_fp8(p, dtype_code(k), cur_stream());
+}
+
 // qkv decode projection: returns the rotated q [M, ng * r * hd]; k / v rows go
 // to kcache / vcache [L, B, ng, hd] (views at the batch offset) at the slot
 // `slot_t` (int64 device scalar) or `slot`.
@@ -806,10 +861,16 @@ at::Tensor skinny_qkv_rope_cache(const at::Tensor& x, const at::Tensor& w,
                                  const at::Tensor& sin, const at::Tensor& pos, at::Tensor kcache,
                                  at::Tensor vcache, const c10::optional<at::Tensor>& slot_t,
                                  int64_t slot, bool packed,
-                                 const c10::optional<at::Tensor>& w_scale) {
+                                 const c10::optional<at::Tensor>& w_scale,
+                                 const c10::optional<at::Tensor>& kv_scale) {
   auto p = skinny_args(x, w, norm_w, eps, packed, w_scale);
   const int64_t N = w.size(0);
   TORCH_CHECK(N == ng * (r + 2) * hd && hd % 8 == 0, "skinny qkv: w rows != ng * (r + 2) * hd");
+  // FP8 KV cache: uint8 (e4m3fn) caches and fp32 scales [2, ng]
+  const auto cache_t = kv_scale ? at::kByte : x.scalar_type();
+  if (kv_scale) p.kv_scale = kv_scale_ptr(*kv_scale, ng, x);
+  else TORCH_CHECK(kcache.scalar_type() != at::kByte && vcache.scalar_type() != at::kByte,
+                   "skinny qkv: an FP8 (uint8) cache needs its kv_scale tensor");
   TORCH_CHECK(ema::skinny_gemm_supported(p.M, N, p.K), "skinny qkv: unsupported shape");
   TORCH_CHECK(cos.is_cuda() && sin.is_cuda() && cos.scalar_type() == at::kFloat &&
               sin.scalar_type() == at::kFloat && cos.is_contiguous() && sin.is_contiguous() &&
@@ -817,7 +878,7 @@ at::Tensor skinny_qkv_rope_cache(const at::Tensor& x, const at::Tensor& w,
   TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kLong && pos.size(0) == p.M,
               "skinny qkv: pos int64 with one row per token");
   for (const at::Tensor* c : {&kcache, &vcache}) {
-    TORCH_CHECK(c->is_cuda() && c->scalar_type() == x.scalar_type() && c->dim() == 4 &&
+    TORCH_CHECK(c->is_cuda() && c->scalar_type() == cache_t && c->dim() == 4 &&
                 c->size(1) >= p.M && c->size(2) == ng && c->size(3) == hd && c->stride(3) == 1 &&
                 c->stride(2) == hd, "skinny qkv: caches [L, B, ng, hd] with packed heads");
   }
@@ -855,18 +916,27 @@ void flash_decode(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                   int64_t b, int64_t sk, int64_t nq, int64_t nkv, int64_t hd,
                   std::vector<int64_t> qs, std::vector<int64_t> ks, std::vector<int64_t> vs,
                   std::vector<int64_t> os, double scale, const c10::optional<at::Tensor>& kv_len,
-                  int64_t kpw, int64_t window) {
+                  int64_t kpw, int64_t window, const c10::optional<at::Tensor>& kv_scale) {
   check_gpu(q, "q");
   TORCH_CHECK(window >= 0, "sliding window must be >= 0 (0: none)");
+  // FP8 KV cache: k / v uint8 (e4m3fn bytes) with fp32 scales [2, nkv]
+  const bool kv8 = k.scalar_type() == at::kByte || v.scalar_type() == at::kByte;
+  TORCH_CHECK(k.scalar_type() == v.scalar_type(), "k / v cache dtypes differ");
+  TORCH_CHECK(kv8 == kv_scale.has_value(), kv8 ? "an FP8 (uint8) cache needs its kv_scale tensor"
+                                               : "kv_scale given for a 16-bit cache");
+  const auto cache_t = kv8 ? at::kByte : q.scalar_type();
   if (kv_len) {
     TORCH_CHECK(kv_len->is_cuda() && kv_len->scalar_type() == at::kInt && kv_len->numel() >= 1,
                 "kv_len must be a device int32 tensor");
     TORCH_CHECK(kv_len->device() == q.device(), "kv_len on another device");
   }
-  TORCH_CHECK(k.scalar_type() == q.scalar_type() && v.scalar_type() == q.scalar_type() &&
+  TORCH_CHECK(k.scalar_type() == cache_t && v.scalar_type() == cache_t &&
               out.scalar_type() == q.scalar_type(), "q/k/v/out dtype mismatch");
+  TORCH_CHECK(k.is_cuda() && v.is_cuda() && k.device() == q.device() && v.device() == q.device(),
+              "k / v on another device");
   TORCH_CHECK(ema::flash_attn_supported((int)hd, dtype_code(q)), "decode attention supports "
               "bf16/fp16 with head_dim 64 or 128");
+  if (kv8) for (int64_t s : vs) TORCH_CHECK(s % 4 == 0, "FP8 v strides must keep dword alignment");
   TORCH_CHECK(nkv > 0 && nq % nkv == 0 && b > 0 && sk > 0, "bad decode shape");
   TORCH_CHECK(q.stride(-1) == 1 && k.stride(-1) == 1 && v.stride(-1) == 1 && out.stride(-1) == 1,
               "head_dim must be contiguous");
@@ -890,6 +960,11 @@ void flash_decode(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
   p.o_sb = os[0]; p.o_sh = os[2];
   p.scale = (float)scale;
   p.kv_len = kv_len ? kv_len->data_ptr<int>() : nullptr;
+  if (kv8) {
+    p.kv_fp8 = 1;
+    p.k_scale = kv_scale_ptr(*kv_scale, nkv, q);
+    p.v_scale = p.k_scale + nkv;
+  }
   // keys per wave: auto (the largest of 64 / 16 / 8 whose grid covers the chip) or forced (A/B)
   if (kpw <= 0) kpw = ema::flash_decode_kpw((int)b, (int)sk, (int)nq, (int)nkv);
   TORCH_CHECK(kpw == 8 || kpw == 16 || kpw == 64, "decode attention: kpw must be 8, 16 or 64");
@@ -1401,7 +1476,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_decode", &flash_decode, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"),
         py::arg("b"), py::arg("sk"), py::arg("nq"), py::arg("nkv"), py::arg("hd"), py::arg("qs"),
         py::arg("ks"), py::arg("vs"), py::arg("os"), py::arg("scale"), py::arg("kv_len"),
-        py::arg("kpw") = 0, py::arg("window") = 0);
+        py::arg("kpw") = 0, py::arg("window") = 0, py::arg("kv_scale") = py::none());
+  m.def("kv_store_fp8", &kv_store_fp8, py::arg("k"), py::arg("v"), py::arg("kcache"),
+        py::arg("vcache"), py::arg("kv_scale"), py::arg("slot_t") = py::none(),
+        py::arg("slot") = 0);
   m.def("skinny_gemm", &skinny_gemm, py::arg("x"), py::arg("w"), py::arg("packed") = false,
         py::arg("w_scale") = py::none());
   m.def("skinny_gemm_supported", &skinny_gemm_supported);
@@ -1416,7 +1494,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("norm_w"), py::arg("eps"), py::arg("ng"), py::arg("r"), py::arg("hd"),
         py::arg("cos"), py::arg("sin"), py::arg("pos"), py::arg("kcache"), py::arg("vcache"),
         py::arg("slot_t"), py::arg("slot"), py::arg("packed") = false,
-        py::arg("w_scale") = py::none());
+        py::arg("w_scale") = py::none(), py::arg("kv_scale") = py::none());
   m.def("transpose16", &transpose16);
   m.def("transpose16_supported", &transpose16_supported);
 }

@@ -35,6 +35,11 @@
 // and small grids (nq * b < 256); MHA with a full grid stays on FlashAttention
 // (profiles/r2c_decode_bench.txt).
 //
+// FP8 KV cache (--inference_fp8_kv_cache): the KV8 forms of the kernel read a
+// cache of e4m3 bytes with an fp32 scale per KV head (half the stream), and
+// kv_store_fp8_k at the end of the file quantises new K / V rows into it;
+// every decode step over such a cache runs here (ops/fp8_kv.py).
+//
 // Reference: megatron/text_generation/forward_step.py drives the per-token
 // forward; the reference decodes through the training attention path.
 #include <type_traits>
@@ -51,13 +56,45 @@ namespace {
 // KPW: keys per wave (chunk = 4 KPW keys per workgroup), picked per launch
 // so that the grid covers the chip (decode_chunk).
 
-template <typename T, int HD, int RH, int KPW>
+typedef __attribute__((ext_vector_type(2))) float f2;
+
+// 4 e4m3fn bytes of one dword -> fp32 (v_cvt_pk_f32_fp8, exact)
+__device__ __forceinline__ void e4m3x4(uint32_t w, float* f) {
+  const f2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
+  const f2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
+  f[0] = lo[0]; f[1] = lo[1]; f[2] = hi[0]; f[3] = hi[1];
+}
+
+// KV8: the cache holds e4m3fn bytes, value = byte * scale of its KV head
+// (DecodeParams::kv_fp8).  Same grid, chunking and combine; what differs:
+//   * a K piece of 8 dims is an 8-byte load, expanded with v_cvt_pk_f32_fp8 in
+//     both scorers; the head's K scale multiplies the score scale;
+//   * P.V: a V row is HD bytes, so lane = 4 dims (one dword) and a wave
+//     instruction covers VR = 256 / HD rows; the VR row groups' sums meet in
+//     a fixed-order butterfly before the 4-wave LDS step; the head's V scale
+//     multiplies the final normalisation.
+//     (-DEMA_DECODE_FP8_V_NARROW builds the 16-bit mapping instead, lane = head-dim
+//     pair with 2-byte / 1-byte loads, one row per instruction: the A/B of
+//     profiles/r13a_fp8_kv_cache.txt)
+#ifdef EMA_DECODE_FP8_V_NARROW
+constexpr bool kFp8VWide = false;
+#else
+constexpr bool kFp8VWide = true;
+#endif
+
+template <typename T, int HD, int RH, int KPW, bool KV8>
 __global__ __launch_bounds__(256) void decode_attn_k(const DecodeParams p) {
   constexpr int DCH = 4 * KPW;
-  constexpr int HP = HD / 64;  // head-dim elements per lane in P.V (1 or 2)
+  constexpr bool V4 = KV8 && kFp8VWide;
+  constexpr int HP = V4 ? 4 : HD / 64;  // head-dim elements per lane in P.V (1 or 2; KV8: 4)
+  constexpr int VR = V4 ? 256 / HD : 1;  // V rows per wave instruction
+  constexpr int VL = 64 / VR;             // lanes per V row
   typedef typename fa::MT<T>::x8 x8;
+  typedef std::conditional_t<KV8, uint8_t, T> KT;   // cache element
+  typedef std::conditional_t<KV8, uint2, x8> kpiece;  // 8 dims of one K row
   // HP consecutive 16-bit values of one V row (one dword at hd 128)
-  typedef typename std::conditional<HP == 2, uint32_t, uint16_t>::type vpair;
+  typedef std::conditional_t<KV8 && !V4, std::conditional_t<HP == 2, uint16_t, uint8_t>,
+                             std::conditional_t<HP >= 2, uint32_t, uint16_t>> vpair;
   __shared__ float ps[RH][DCH];
   __shared__ float red[4][RH];
   __shared__ float pacc[4][RH][HD];
@@ -76,7 +113,16 @@ __global__ __launch_bounds__(256) void decode_attn_k(const DecodeParams p) {
   const int klo = p.window > 0 ? max(sk - p.window, 0) : 0;
   // <= 0: chunk past the cached length (graph decode) or below the window
   const int nk = k0 + DCH <= klo ? 0 : min(DCH, sk - k0);
-  const float sl2 = p.scale * 1.4426950408889634f;
+  float sl2 = p.scale * 1.4426950408889634f;
+  float vsc = 1.f;
+  if constexpr (KV8) {
+    sl2 *= p.k_scale[g];
+    vsc = p.v_scale[g];
+  }
+  auto ldk = [](const KT* a) -> kpiece {
+    if constexpr (KV8) return *reinterpret_cast<const uint2*>(a);
+    else return fa::ld8(a);
+  };
   const int nsplit = gridDim.x;
 
   float mx[RH];
@@ -94,24 +140,28 @@ __global__ __launch_bounds__(256) void decode_attn_k(const DecodeParams p) {
     constexpr int LPK = HD / 8, KPI = 64 / LPK, NI = LK ? 1 : KPW / KPI;
     static_assert(LK || (NI >= 1 && NI <= LPK), "keys per wave vs key rows per instruction");
     const int kl = lane / LPK, dc = LK ? 0 : 8 * (lane % LPK);
-    const T* kbase = (const T*)p.k + (int64_t)b * p.k_sb + (int64_t)g * p.k_sg + dc;
-    x8 kv[NI];
+    const KT* kbase = (const KT*)p.k + (int64_t)b * p.k_sb + (int64_t)g * p.k_sg + dc;
+    kpiece kv[NI];
     if constexpr (!LK) {
 #pragma unroll
       for (int i = 0; i < NI; ++i) {
         const int kk = min(wave * KPW + i * KPI + kl, nk - 1);
-        kv[i] = fa::ld8(kbase + (int64_t)(k0 + kk) * p.k_ss);
+        kv[i] = ldk(kbase + (int64_t)(k0 + kk) * p.k_ss);
       }
     }
     // V rows in flight per lane: the whole wave's keys for 1-2 heads per
     // workgroup; with 4-8 heads the score / P.V registers leave room for 8
-    constexpr int VU = (RH <= 2 || KPW <= 8) ? KPW : 8;
+    // (KV8: KPW / VR loads cover the wave's keys, load u the rows VR u + vg)
+    constexpr int NV = KPW / VR;
+    constexpr int VU = (RH <= 2 || NV <= 8) ? NV : 8;
+    static_assert(NV >= 1 && NV % VU == 0, "V rows per instruction vs keys per wave");
     vpair vv[VU];
-    const T* vbase = (const T*)p.v + (int64_t)b * p.v_sb + (int64_t)g * p.v_sg + HP * lane;
+    const int vg = lane / VL;  // this lane's V row within an instruction (KV8)
+    const KT* vbase = (const KT*)p.v + (int64_t)b * p.v_sb + (int64_t)g * p.v_sg + HP * (lane % VL);
     auto load_v = [&](int u0) {
 #pragma unroll
       for (int u = 0; u < VU; ++u) {
-        const int kc = min(k0 + wave * KPW + u0 + u, k0 + nk - 1);
+        const int kc = min(k0 + wave * KPW + VR * (u0 + u) + vg, k0 + nk - 1);
         vv[u] = *reinterpret_cast<const vpair*>(vbase + (int64_t)kc * p.v_ss);
       }
     };
@@ -141,7 +191,7 @@ __global__ __launch_bounds__(256) void decode_attn_k(const DecodeParams p) {
     // lane; one gather hands lane L < KPW the score of the wave's key L
     float s[RH];
     if constexpr (LK) {
-      const T* krow = kbase + (int64_t)(k0 + min(wave * KPW + lane, nk - 1)) * p.k_ss;
+      const KT* krow = kbase + (int64_t)(k0 + min(wave * KPW + lane, nk - 1)) * p.k_ss;
 #pragma unroll
       for (int j = 0; j < RH; ++j) s[j] = 0.f;
       // (the branch and the 4-chunk rolled loop keep hipcc from hoisting all
@@ -149,17 +199,24 @@ __global__ __launch_bounds__(256) void decode_attn_k(const DecodeParams p) {
       if (lane < KPW && wave * KPW + lane < nk) {
 #pragma unroll 1
         for (int c0 = 0; c0 < HD / 8; c0 += 4) {
-          x8 kc8[4];
+          kpiece kc8[4];
 #pragma unroll
-          for (int c = 0; c < 4; ++c) kc8[c] = fa::ld8(krow + 8 * (c0 + c));
+          for (int c = 0; c < 4; ++c) kc8[c] = ldk(krow + 8 * (c0 + c));
 #pragma unroll
-          for (int c = 0; c < 4; ++c)
+          for (int c = 0; c < 4; ++c) {
+            float kf[8];
+            if constexpr (KV8) {
+              e4m3x4(kc8[c].x, kf);
+              e4m3x4(kc8[c].y, kf + 4);
+            } else {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              const float kf = (float)kc8[c][e];
-#pragma unroll
-              for (int j = 0; j < RH; ++j) s[j] = __builtin_fmaf(kf, qs[j][8 * (c0 + c) + e], s[j]);
+              for (int e = 0; e < 8; ++e) kf[e] = (float)kc8[c][e];
             }
+#pragma unroll
+            for (int e = 0; e < 8; ++e)
+#pragma unroll
+              for (int j = 0; j < RH; ++j) s[j] = __builtin_fmaf(kf[e], qs[j][8 * (c0 + c) + e], s[j]);
+          }
         }
       }
     }
@@ -169,8 +226,16 @@ __global__ __launch_bounds__(256) void decode_attn_k(const DecodeParams p) {
 #pragma unroll
       for (int i = 0; i < NI; ++i) {
         float d = 0.f;
+        if constexpr (KV8) {
+          float kf[8];
+          e4m3x4(kv[i].x, kf);
+          e4m3x4(kv[i].y, kf + 4);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) d = __builtin_fmaf((float)kv[i][e], (float)qv[j][e], d);
+          for (int e = 0; e < 8; ++e) d = __builtin_fmaf(kf[e], (float)qv[j][e], d);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) d = __builtin_fmaf((float)kv[i][e], (float)qv[j][e], d);
+        }
         v[i] = d;
       }
 #pragma unroll
@@ -223,26 +288,49 @@ __global__ __launch_bounds__(256) void decode_attn_k(const DecodeParams p) {
 #pragma unroll
       for (int e = 0; e < HP; ++e) acc[j][e] = 0.f;
 #pragma unroll 1
-    for (int u0 = 0; u0 < KPW; u0 += VU) {
+    for (int u0 = 0; u0 < NV; u0 += VU) {
       if (u0 > 0) load_v(u0);
 #pragma unroll
       for (int u = 0; u < VU; ++u) {
-        const int kc = wave * KPW + u0 + u;
+        const int kc = wave * KPW + VR * (u0 + u) + vg;
+        float vf[HP];
+        if constexpr (V4) {
+          e4m3x4(vv[u], vf);
+        } else if constexpr (KV8) {
+          const f2 c = __builtin_amdgcn_cvt_pk_f32_fp8((int)vv[u], false);
+#pragma unroll
+          for (int e = 0; e < HP; ++e) vf[e] = c[e];
+        } else {
+#pragma unroll
+          for (int e = 0; e < HP; ++e) {
+            const uint16_t bits = (uint16_t)(vv[u] >> (16 * e));
+            vf[e] = (float)__builtin_bit_cast(T, bits);
+          }
+        }
 #pragma unroll
         for (int j = 0; j < RH; ++j) {
           const float pj = ps[j][kc];
 #pragma unroll
-          for (int e = 0; e < HP; ++e) {
-            const uint16_t bits = (uint16_t)(vv[u] >> (16 * e));
-            acc[j][e] = __builtin_fmaf(pj, (float)__builtin_bit_cast(T, bits), acc[j][e]);
-          }
+          for (int e = 0; e < HP; ++e) acc[j][e] = __builtin_fmaf(pj, vf[e], acc[j][e]);
         }
       }
     }
+    if constexpr (V4) {
+      // the VR row groups of the wave: xor butterfly, the same tree in every
+      // lane (a + b is commutative), so the sum does not depend on the lane
 #pragma unroll
-    for (int j = 0; j < RH; ++j)
+      for (int o = VL; o < 64; o <<= 1)
 #pragma unroll
-      for (int e = 0; e < HP; ++e) pacc[wave][j][HP * lane + e] = acc[j][e];
+        for (int j = 0; j < RH; ++j)
+#pragma unroll
+          for (int e = 0; e < HP; ++e) acc[j][e] += __shfl_xor(acc[j][e], o, 64);
+    }
+    if (lane < VL) {
+#pragma unroll
+      for (int j = 0; j < RH; ++j)
+#pragma unroll
+        for (int e = 0; e < HP; ++e) pacc[wave][j][HP * lane + e] = acc[j][e];
+    }
     __syncthreads();
 
     if (nsplit == 1) {  // one chunk holds every key: normalise and write O here
@@ -251,7 +339,7 @@ __global__ __launch_bounds__(256) void decode_attn_k(const DecodeParams p) {
         const int head = g * r + h0 + j;
         const float l = red[0][j] + red[1][j] + red[2][j] + red[3][j];
         const float o = pacc[0][j][d] + pacc[1][j][d] + pacc[2][j][d] + pacc[3][j][d];
-        ((T*)p.o)[(int64_t)b * p.o_sb + (int64_t)head * p.o_sh + d] = (T)(l > 0.f ? o / l : 0.f);
+        ((T*)p.o)[(int64_t)b * p.o_sb + (int64_t)head * p.o_sh + d] = (T)(l > 0.f ? (KV8 ? o / l * vsc : o / l) : 0.f);
       }
       return;
     }
@@ -327,7 +415,7 @@ __global__ __launch_bounds__(256) void decode_attn_k(const DecodeParams p) {
         o = __builtin_fmaf(ov[u], w, o);
       }
     }
-    ((T*)p.o)[(int64_t)b * p.o_sb + (int64_t)head * p.o_sh + d] = (T)(L > 0.f ? o / L : 0.f);
+    ((T*)p.o)[(int64_t)b * p.o_sb + (int64_t)head * p.o_sh + d] = (T)(L > 0.f ? (KV8 ? o / L * vsc : o / L) : 0.f);
   }
 }
 
@@ -346,27 +434,77 @@ int decode_kpw_auto(int b, int sk, int nq, int nkv) {
   return grid(16) >= 128 ? 16 : 8;  // b = 1 MHA, 256 keys: 16 -> 7.0 us, 8 -> 7.4 (r4t_kpw)
 }
 
-template <typename T, int HD, int RH>
+template <typename T, int HD, int RH, bool KV8>
 void launch_rh(const DecodeParams& p, int kpw, hipStream_t s) {
   const int r = p.nq / p.nkv, nhs = (r + RH - 1) / RH;
   const int nsplit = (p.sk + 4 * kpw - 1) / (4 * kpw);
   const dim3 grid(nsplit, p.nkv * nhs, p.b);
-  if (kpw == 64) hipLaunchKernelGGL((decode_attn_k<T, HD, RH, 64>), grid, dim3(256), 0, s, p);
-  else if (kpw == 16) hipLaunchKernelGGL((decode_attn_k<T, HD, RH, 16>), grid, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL((decode_attn_k<T, HD, RH, 8>), grid, dim3(256), 0, s, p);
+  if (kpw == 64) hipLaunchKernelGGL((decode_attn_k<T, HD, RH, 64, KV8>), grid, dim3(256), 0, s, p);
+  else if (kpw == 16) hipLaunchKernelGGL((decode_attn_k<T, HD, RH, 16, KV8>), grid, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((decode_attn_k<T, HD, RH, 8, KV8>), grid, dim3(256), 0, s, p);
+}
+
+template <typename T, int HD, bool KV8>
+void launch_kv(const DecodeParams& p, hipStream_t s) {
+  const int r = p.nq / p.nkv;
+  const int kpw = p.kpw;
+  if (r >= 8) launch_rh<T, HD, 8, KV8>(p, kpw, s);
+  else if (r >= 4) launch_rh<T, HD, 4, KV8>(p, kpw, s);
+  else if (r >= 2) launch_rh<T, HD, 2, KV8>(p, kpw, s);
+  else launch_rh<T, HD, 1, KV8>(p, kpw, s);
 }
 
 template <typename T, int HD>
 void launch(const DecodeParams& p, hipStream_t s) {
-  const int r = p.nq / p.nkv;
-  const int kpw = p.kpw;
-  if (r >= 8) launch_rh<T, HD, 8>(p, kpw, s);
-  else if (r >= 4) launch_rh<T, HD, 4>(p, kpw, s);
-  else if (r >= 2) launch_rh<T, HD, 2>(p, kpw, s);
-  else launch_rh<T, HD, 1>(p, kpw, s);
+  if (p.kv_fp8) launch_kv<T, HD, true>(p, s);
+  else launch_kv<T, HD, false>(p, s);
+}
+
+// Quantising store of new K / V rows into the e4m3 cache (KvStoreParams):
+// thread = 8 consecutive dims of one (token, sequence, head): a 16-B load, 8
+// clamped fp32 values, 4 v_cvt_pk_fp8_f32 (RNE; the clamp first, since the
+// convert alone turns an overflow into NaN) and one 8-B store.  blockIdx.y:
+// 0 = K, 1 = V.
+template <typename T>
+__global__ __launch_bounds__(256) void kv_store_fp8_k(const KvStoreParams p) {
+  const int c8 = p.hd / 8;
+  const int64_t n = (int64_t)p.sq * p.b * p.nkv * c8;
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const bool isv = blockIdx.y != 0;
+  const int c = (int)(i % c8);
+  int64_t t = i / c8;
+  const int g = (int)(t % p.nkv);
+  t /= p.nkv;
+  const int bb = (int)(t % p.b);
+  const int64_t s = t / p.b;
+  const T* src = (const T*)(isv ? p.v : p.k) + s * (isv ? p.v_ss : p.k_ss) +
+                 (int64_t)bb * (isv ? p.v_sb : p.k_sb) + (int64_t)g * (isv ? p.v_sg : p.k_sg) + 8 * c;
+  const typename fa::MT<T>::x8 x = fa::ld8(src);
+  const float inv = 1.0f / p.scales[(isv ? p.nkv : 0) + g];
+  const int64_t slot = p.slot_ptr ? *p.slot_ptr : p.slot;
+  float f[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) f[e] = fminf(fmaxf((float)x[e] * inv, -448.f), 448.f);
+  int lo = 0, hi = 0;
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
+  uint8_t* dst = (isv ? p.vcache : p.kcache) + (slot + s) * p.c_ss + (int64_t)bb * p.c_sb +
+                 (int64_t)g * p.hd + 8 * c;
+  *reinterpret_cast<uint2*>(dst) = make_uint2((unsigned)lo, (unsigned)hi);
 }
 
 }  // namespace
+
+void kv_store_fp8(const KvStoreParams& p, int dt, hipStream_t s) {
+  const int64_t n = (int64_t)p.sq * p.b * p.nkv * (p.hd / 8);
+  if (n == 0) return;
+  const dim3 grid((unsigned)((n + 255) / 256), 2);
+  if (dt == DT_BF16) hipLaunchKernelGGL(kv_store_fp8_k<bf16>, grid, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(kv_store_fp8_k<fp16>, grid, dim3(256), 0, s, p);
+}
 
 int flash_decode_kpw(int b, int sk, int nq, int nkv) { return decode_kpw_auto(b, sk, nq, nkv); }
 int flash_decode_splits(int sk, int kpw) { return (sk + 4 * kpw - 1) / (4 * kpw); }

@@ -219,8 +219,32 @@ struct DecodeParams {
   int kpw;  // keys per wave: 64 / 16 / 8 (flash_decode_kpw picks; chunk = 4 kpw keys)
   // sliding window (0: none): of the n valid keys only [max(0, n - window), n) count
   int window;
+  // FP8 KV cache (--inference_fp8_kv_cache): k / v hold OCP e4m3fn bytes
+  // (strides in bytes) and value = byte * scale of its KV head; the scales are
+  // device fp32 [nkv], read by the kernel (a captured graph sees later changes)
+  int kv_fp8;
+  const float* k_scale;
+  const float* v_scale;
 };
 int flash_decode_kpw(int b, int sk, int nq, int nkv);
+
+// Quantising KV-cache store: k / v [sq, b, nkv, hd] of dt (element strides
+// *_ss / *_sb / *_sg, hd contiguous) -> e4m3fn rows slot .. slot + sq - 1 of
+// the caches [L, B, nkv, hd] (byte strides c_ss / c_sb, packed heads), slot
+// from *slot_ptr when given.  byte = e4m3_rne(clamp(x / scale[head], +-448)),
+// scales fp32 [2, nkv] (row 0: K, row 1: V).  One launch covers K and V.
+struct KvStoreParams {
+  const void* k;
+  const void* v;
+  uint8_t* kcache;
+  uint8_t* vcache;
+  int64_t k_ss, k_sb, k_sg, v_ss, v_sb, v_sg, c_ss, c_sb;
+  int sq, b, nkv, hd;
+  int64_t slot;
+  const int64_t* slot_ptr;
+  const float* scales;
+};
+void kv_store_fp8(const KvStoreParams& p, int dt, hipStream_t s);
 
 // ---- decode_tail.hip -----------------------------------------------------------------------------
 // Graphed greedy decode step tail: argmax of each row of logits [b, V] (row
@@ -353,6 +377,10 @@ struct SkinnyArgs {
   // order: [N], GLU [2N] up rows then gate rows) multiplies the fp32 sums
   // before the epilogue's first rounding.  nullptr: the 16-bit paths.
   const float* w_scale;
+  // EPI_QKV, FP8 KV cache: non-null = the caches hold e4m3fn bytes (c_ss / c_sb
+  // in bytes) and kv_scale is fp32 [2, ng] (row 0: K, row 1: V); a k / v value
+  // is stored as e4m3_rne(clamp(x / scale, +-448)).  nullptr: 16-bit caches.
+  const float* kv_scale;
 };
 void skinny_gemm_ex(const SkinnyArgs& p, int epi, int dt, hipStream_t s);
 int skinny_glu_half_tail(int64_t F, int64_t K, bool norm, int64_t M);

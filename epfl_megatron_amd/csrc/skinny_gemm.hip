@@ -111,7 +111,17 @@ struct EpiPre {
   int pos = 0;       // (32-bit: two row blocks' 64-bit positions and slots spilled)
   int64_t slot = 0;  // uniform: scalar registers
   f4 sc = {1.f, 1.f, 1.f, 1.f};  // W8: the scales of the lane's 4 W rows (epi_scale)
+  float kvr = 1.f;  // FP8 KV cache: 1 / scale of the lane's k / v head (kv_rscale)
 };
+
+// FP8 KV cache: the reciprocal scale of the k (h == r) or v (h == r + 1) head
+// of group g; q heads store no cache value
+__device__ __forceinline__ float kv_rscale(const SkinnyArgs& p, int n) {
+  const int per_g = (p.r + 2) * p.hd, g = n / per_g, h = (n - g * per_g) / p.hd;
+  if (h < p.r) return 1.f;
+  const int ng = p.N / per_g;
+  return 1.0f / p.kv_scale[(h - p.r) * ng + g];
+}
 
 // W8: the reduced fp32 tile times the row scales, in front of the epilogue's
 // first rounding.  The product is handed on as an opaque value so that the
@@ -171,6 +181,7 @@ __device__ __forceinline__ void epi_prefetch(const SkinnyArgs& p, int blk, int l
       e.c[j] = cr[j];
       e.s[j] = sr[j];
     }
+    if (p.kv_scale) e.kvr = kv_rscale(p, n);
   }
 }
 
@@ -230,6 +241,21 @@ __device__ __forceinline__ void epilogue(const SkinnyArgs& p, int blk, const f4&
       dst = y + (int64_t)m * p.ldy + (int64_t)(g * p.r + h) * hd + d;
     } else {
       const int64_t slot = use_pre ? pre.slot : p.slot_ptr ? *p.slot_ptr : p.slot;
+      if (p.kv_scale) {
+        // e4m3 cache: the lane's 4 consecutive dims of one token and head, as
+        // rounded to T above, scaled, clamped (the convert alone turns an
+        // overflow into NaN), packed and stored as one dword
+        const float inv = use_pre ? pre.kvr : kv_rscale(p, n);
+        float f[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) f[i] = fminf(fmaxf((float)o[i] * inv, -448.f), 448.f);
+        int w = 0;
+        w = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], w, false);
+        w = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w, true);
+        uint8_t* c8 = (uint8_t*)(h == p.r ? p.kcache : p.vcache);
+        *reinterpret_cast<int*>(c8 + slot * p.c_ss + (int64_t)m * p.c_sb + (int64_t)g * hd + d) = w;
+        return;
+      }
       T* cache = (T*)(h == p.r ? p.kcache : p.vcache);
       dst = cache + slot * p.c_ss + (int64_t)m * p.c_sb + (int64_t)g * hd + d;
     }

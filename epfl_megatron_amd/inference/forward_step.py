@@ -30,6 +30,20 @@ class InferenceParams:
         # token (int64 [1]) and the valid key count (int32 [1]) on the device
         self.device_offset = None
         self.device_kv_len = None
+        # FP8 KV cache (--inference_fp8_kv_cache): per layer an fp32 device
+        # tensor [2, nkv_per_tp] (row 0: K scales, row 1: V scales), 1.0 until
+        # set; the kernels read it from device memory on every launch
+        self.kv_scale_dict = {}
+
+    def set_kv_scales(self, layer, k_scale=None, v_scale=None):
+        """Set the per-head e4m3 scales of ``layer``'s cache in place (values
+        broadcastable to ``[nkv_per_tp]``; None keeps a row).  What the cache
+        already holds was quantised with the old scales, so set them before the
+        prefill."""
+        sc = self.kv_scale_dict[layer]
+        for row, val in ((0, k_scale), (1, v_scale)):
+            if val is not None:
+                sc[row].copy_(torch.as_tensor(val, dtype=torch.float32).to(sc.device).expand_as(sc[row]))
 
     def swap_key_value_dict(self, batch_idx):
         """Reorder the cached batch rows (beam search keeps the best beams)."""

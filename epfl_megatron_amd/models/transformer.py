@@ -37,7 +37,7 @@ from ..ops._ext import use_native, ext
 from ..parallel.context import chunk_position_ids, ring_attention
 from ..ops.attention import flash_attn_qkvpacked, flash_attn_func, flash_decode_cached
 from ..ops.activations import glu, bias_gelu, gelu
-from ..ops import decode_pack, fp8_weights
+from ..ops import decode_pack, fp8_kv, fp8_weights
 from ..ops.softmax import FusedScaleMaskSoftmax
 from .enums import AttnMaskType, AttnType, LayerType, ModelType, PositionEmbeddingType
 from .module import MegatronModule
@@ -61,6 +61,24 @@ def set_fp8_weights(on):
     """Switch FP8 weight-only decode for every fused decode layer of the process."""
     global _FP8_WEIGHTS
     _FP8_WEIGHTS = bool(on)
+
+
+# FP8 KV cache (--inference_fp8_kv_cache, opt-in): caches allocated under the
+# switch hold e4m3 bytes with a scale per KV head (ops/fp8_kv.py); the decode
+# steps read them in csrc/flash_decode.hip's FP8 forms.  With calibration
+# (--inference_fp8_kv_calibrate) the prefill that restarts a cache sets the
+# scales from the prompt; else they stay 1.0.
+_FP8_KV = os.environ.get("EMA_FP8_KV", "0") == "1"
+_FP8_KV_CALIBRATE = os.environ.get("EMA_FP8_KV_CALIBRATE", "0") == "1"
+
+
+def set_fp8_kv_cache(on, calibrate=None):
+    """Switch the FP8 KV cache for every cache allocated from now on (and,
+    with ``calibrate``, the prompt calibration of its scales)."""
+    global _FP8_KV, _FP8_KV_CALIBRATE
+    _FP8_KV = bool(on)
+    if calibrate is not None:
+        _FP8_KV_CALIBRATE = bool(calibrate)
 
 
 def _linear_kwargs(args):
@@ -309,8 +327,60 @@ class ParallelAttention(MegatronModule):
     def _allocate_kv(self, max_len, max_batch, device):
         shape = (max_len, max_batch, self.num_groups_per_partition,
                  self.hidden_size_per_attention_head)
+        if _FP8_KV:  # e4m3 bytes (zeroed: an unwritten row must not read as NaN)
+            return (torch.zeros(shape, dtype=torch.uint8, device=device),
+                    torch.zeros(shape, dtype=torch.uint8, device=device))
         return (torch.empty(shape, dtype=self.params_dtype, device=device),
                 torch.empty(shape, dtype=self.params_dtype, device=device))
+
+    def _kv_scales(self, ip, device):
+        """This layer's FP8 cache scales (fp32 [2, nkv_per_tp], 1.0 until set),
+        kept on the inference params next to the cache."""
+        d = getattr(ip, "kv_scale_dict", None)
+        if d is None:
+            d = ip.kv_scale_dict = {}
+        if self.layer_number not in d:
+            d[self.layer_number] = fp8_kv.new_scales(self.num_groups_per_partition, device)
+        return d[self.layer_number]
+
+    def _fp8_kv_forward(self, q, k, v, kmem, vmem, attention_mask, ip):
+        """``_inference_forward`` over an FP8 cache: the new rows go through the
+        quantising store; the restart prefill attends over its fresh 16-bit K
+        and V, a decode step on the native path reads the bytes in the FP8
+        decode kernel, and everything else dequantises the slice it needs."""
+        s0, b0 = ip.sequence_len_offset, ip.batch_size_offset
+        sq, b = q.shape[:2]
+        sc = self._kv_scales(ip, q.device)
+        kc, vc = kmem[:, b0:b0 + b], vmem[:, b0:b0 + b]
+        native = use_native(q) and q.shape[-1] in (64, 128)
+        if getattr(ip, "device_offset", None) is not None and sq == 1:
+            if q.is_cuda and not native:
+                raise NotImplementedError("hipGraph decode needs the native decode attention "
+                                          "kernel (GPU, bf16/fp16, head_dim 64 or 128)")
+            fp8_kv.store(k, v, kc, vc, sc, slot_t=ip.device_offset)
+            o = flash_decode_cached(q.transpose(0, 1), kc.transpose(0, 1), vc.transpose(0, 1),
+                                    ip.device_kv_len, window=self._window(kc.shape[0]),
+                                    kv_scale=sc)
+            return o.transpose(0, 1).reshape(sq, b, -1)
+        if s0 == 0 and b0 == 0 and _FP8_KV_CALIBRATE:
+            fp8_kv.calibrate_(sc, k, v)
+        fp8_kv.store(k, v, kc, vc, sc, slot=s0)
+        if sq == 1 and native and self.use_flash_attn:
+            o = flash_decode_cached(q.transpose(0, 1), kc[:s0 + 1].transpose(0, 1),
+                                    vc[:s0 + 1].transpose(0, 1), None,
+                                    window=self._window(s0 + 1), kv_scale=sc)
+            return o.transpose(0, 1).reshape(sq, b, -1)
+        if s0 == 0:
+            keys, vals = k, v
+        else:
+            keys = fp8_kv.dequantize(kc[:s0 + sq], sc[0], q.dtype)
+            vals = fp8_kv.dequantize(vc[:s0 + sq], sc[1], q.dtype)
+        if self.use_flash_attn:
+            o = flash_attn_func(q.transpose(0, 1), keys.transpose(0, 1), vals.transpose(0, 1),
+                                causal=True, window=self._window(s0 + sq))
+            return o.transpose(0, 1).reshape(sq, b, -1)
+        return self.core_attention(q, self._expand_kv(keys), self._expand_kv(vals),
+                                   attention_mask)
 
     def _core(self, q, k, v, attention_mask):
         if self.checkpoint_core_attention and self.training:
@@ -392,6 +462,8 @@ class ParallelAttention(MegatronModule):
             # Rotate with the true positions BEFORE caching (fixes D1).
             q = apply_rope_ref(q, rope[0], rope[1], position_ids, offset=s0)
             k = apply_rope_ref(k, rope[0], rope[1], position_ids, offset=s0)
+        if kmem.dtype == torch.uint8:
+            return self._fp8_kv_forward(q, k, v, kmem, vmem, attention_mask, ip)
         if getattr(ip, "device_offset", None) is not None and sq == 1:
             # hipGraph decode step (inference/hip_graph.py): cache slot and key
             # count live in device tensors, so no launch depends on the step
@@ -540,6 +612,8 @@ class ParallelTransformerLayer(MegatronModule):
         kmem, vmem = ip.key_value_memory_dict[sa.layer_number]
         b0, s0 = ip.batch_size_offset, ip.sequence_len_offset
         kc, vc = kmem[:, b0:b0 + b], vmem[:, b0:b0 + b]
+        # FP8 KV cache: the QKV epilogue quantises k / v with these scales
+        kvs = sa._kv_scales(ip, x.device) if kmem.dtype == torch.uint8 else None
         cos, sin = sa._rope(x.device)
         if position_ids is None:
             pos = torch.full((b, 1), s0, dtype=torch.long, device=x.device)
@@ -571,11 +645,16 @@ class ParallelTransformerLayer(MegatronModule):
                                     ln1.eps, ng, r, hd,
                                     cos, sin, pos, kc, vc,
                                     ip.device_offset if graph else None, 0 if graph else s0,
-                                    pq is not None, sq)
+                                    pq is not None, sq, *(() if kvs is None else (kvs,)))
         q4 = q.view(b, 1, ng * r, hd)
         if graph:
             o = flash_decode_cached(q4, kc.transpose(0, 1), vc.transpose(0, 1), ip.device_kv_len,
-                                    window=sa._window(kc.shape[0]))
+                                    window=sa._window(kc.shape[0]), kv_scale=kvs)
+        elif kvs is not None:
+            # FP8 cache: every step reads the bytes in the FP8 decode kernel
+            # (the MHA route to the FlashAttention forward takes 16-bit K / V)
+            o = flash_decode_cached(q4, kc[:s0 + 1].transpose(0, 1), vc[:s0 + 1].transpose(0, 1),
+                                    None, window=sa._window(s0 + 1), kv_scale=kvs)
         else:
             o = flash_attn_func(q4, kc[:s0 + 1].transpose(0, 1), vc[:s0 + 1].transpose(0, 1),
                                 causal=True, window=sa._window(s0 + 1))
@@ -704,6 +783,9 @@ class ParallelTransformer(MegatronModule):
         super().__init__()
         if getattr(args, "inference_fp8_weights", False):
             set_fp8_weights(True)
+        if getattr(args, "inference_fp8_kv_cache", False):
+            set_fp8_kv_cache(True, calibrate=bool(getattr(args, "inference_fp8_kv_calibrate",
+                                                          False)) or None)
         world_size = state.get_tensor_model_parallel_world_size()
         self.layer_type = layer_type
         self.model_type = model_type

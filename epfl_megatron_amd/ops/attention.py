@@ -151,12 +151,14 @@ class _FlashQKVPackedFn(torch.autograd.Function):
         return dqkv5.view(s, b, -1), None, None, None, None, None, None, None, None, None, None
 
 
-def _flash_decode(q, k, v, scale, kv_len=None, window=0):
+def _flash_decode(q, k, v, scale, kv_len=None, window=0, kv_scale=None):
     """sq == 1 against a KV cache (generation): split-key decode kernel
     (``csrc/flash_decode.hip``); no autograd.  ``kv_len``: optional device
     int32 tensor with the number of valid keys (k / v then span the whole
     cache; the launch does not depend on the step, for hipGraph capture).
-    ``window``: only the last ``window`` valid keys count (0: all)."""
+    ``window``: only the last ``window`` valid keys count (0: all).
+    ``kv_scale``: fp32 ``[2, nkv]`` when k / v are an FP8 cache (uint8 e4m3fn
+    bytes, ``ops/fp8_kv.py``)."""
     b, _, nq, d = q.shape
     sk, nkv = k.shape[1], k.shape[2]
     r = nq // nkv
@@ -164,22 +166,29 @@ def _flash_decode(q, k, v, scale, kv_len=None, window=0):
     ext().flash_decode(q, k, v, out, b, sk, nq, nkv, d, list(_bsnd_strides(q, r)),
                        list(_bsnd_strides(k, 1)[:3]), list(_bsnd_strides(v, 1)[:3]),
                        [out.stride(0), out.stride(1), out.stride(2)], float(scale), kv_len,
-                       window=int(window))
+                       window=int(window), kv_scale=kv_scale)
     return out
 
 
-def flash_decode_cached(q, k, v, kv_len, softmax_scale=None, window=0):
+def flash_decode_cached(q, k, v, kv_len, softmax_scale=None, window=0, kv_scale=None):
     """One query row per sequence against a whole KV cache ``k / v [b, smax,
     nkv, d]`` of which the first ``kv_len`` (device int32) keys are valid
-    (with ``window``: the last ``window`` of those)."""
+    (with ``window``: the last ``window`` of those).  ``kv_len`` None: all
+    ``smax`` keys are valid.  ``kv_scale``: fp32 ``[2, nkv]`` when k / v are an
+    FP8 cache (uint8 e4m3fn bytes, ``ops/fp8_kv.py``)."""
     _check_window(window, True)
     if not use_native(q):
-        n = int(kv_len.reshape(-1)[0])
+        n = int(kv_len.reshape(-1)[0]) if kv_len is not None else k.shape[1]
         lo = max(n - window, 0) if window else 0
-        return attention_ref(q, k[:, lo:n], v[:, lo:n], False,
+        k, v = k[:, lo:n], v[:, lo:n]
+        if kv_scale is not None:
+            from . import fp8_kv
+            k = fp8_kv.dequantize(k, kv_scale[0], q.dtype)
+            v = fp8_kv.dequantize(v, kv_scale[1], q.dtype)
+        return attention_ref(q, k, v, False,
                              softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(q.shape[-1]))
     scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(q.shape[-1])
-    return _flash_decode(q, k, v, scale, kv_len, window)
+    return _flash_decode(q, k, v, scale, kv_len, window, kv_scale)
 
 
 class _FlashFn(torch.autograd.Function):

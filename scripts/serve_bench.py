@@ -40,6 +40,8 @@ def main():
                     help="without --graph: sample with inference/sampling.py's eager chain")
     ap.add_argument("--fp8_weights", action="store_true",
                     help="FP8 weight-only decode (--inference_fp8_weights; ops/fp8_weights.py)")
+    ap.add_argument("--fp8_kv_cache", action="store_true",
+                    help="FP8 KV cache (--inference_fp8_kv_cache; ops/fp8_kv.py)")
     a = ap.parse_args()
     sampling = a.top_k > 0 or a.top_p > 0.0 or a.temperature != 1.0
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=os.environ.get("MASTER_PORT", "29561"),
@@ -73,6 +75,8 @@ def main():
             "--global_batch_size", "1", "--train_iters", "1", "--lr", "1e-4"]
     if a.fp8_weights:
         argv.append("--inference_fp8_weights")
+    if a.fp8_kv_cache:
+        argv.append("--inference_fp8_kv_cache")
     initialize_megatron(finetune.extra_args, {"tokenizer_type": "NullTokenizer"}, args_list=argv)
     model = get_model(finetune.model_provider, ModelType.encoder_or_decoder, wrap_with_ddp=False)
     m = model[0].eval()
