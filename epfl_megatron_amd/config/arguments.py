@@ -58,6 +58,14 @@ FLAG_TABLE = {
                    "the bytes per decode step).  Activations, KV cache, LM head, prefill and "
                    "the 16-bit parameters are unchanged.  Changes the outputs by the weight "
                    "quantisation error: opt-in"),
+        _flag("--inference_mxfp4_weights", action="store_true",
+              help="MXFP4 weight-only decode: the fused decode layer streams the QKV, dense, fc1 "
+                   "and fc2 weights as OCP MXFP4 copies (e2m1 values with one power-of-two e8m0 "
+                   "scale per 32 weights along K; ops/mxfp4_weights.py; 4.25 bits per weight "
+                   "per decode step).  Activations, KV cache, LM head, prefill and the 16-bit "
+                   "parameters are unchanged.  Changes the outputs by the 4-bit weight "
+                   "quantisation error (relative RMS about 0.11 on Gaussian weights): opt-in.  "
+                   "Excludes --inference_fp8_weights"),
         _flag("--inference_fp8_kv_cache", action="store_true",
               help="FP8 KV cache: K and V are cached as e4m3 bytes with an fp32 scale per KV "
                    "head (ops/fp8_kv.py; half the cache memory and half the bytes decode "
@@ -404,6 +412,9 @@ def parse_args(extra_args_provider=None, args_list=None):
     if extra_args_provider is not None:
         parser = extra_args_provider(parser)
     args = parser.parse_args(args_list)
+    if getattr(args, "inference_fp8_weights", False) and getattr(args, "inference_mxfp4_weights", False):
+        parser.error("--inference_fp8_weights and --inference_mxfp4_weights are two formats for the "
+                     "same decode weight streams: give one of them")
     args.rank = int(os.getenv("RANK", "0"))
     args.world_size = int(os.getenv("WORLD_SIZE", "1"))
     return args

@@ -691,11 +691,37 @@ static const float* skinny_fp8_scale(const at::Tensor& x, const at::Tensor& w,
   return w_scale.data_ptr<float>();
 }
 
+// MXFP4 weight-only decode (ops/mxfp4_weights.py): a uint8 w_scale selects
+// the format.  w holds the packed e2m1 nibbles [N, K / 2] and w_scale the
+// N K / 32 e8m0 block scales in stream order.  N and K come from x and the
+// logical shape.  Returns the pointer for SkinnyArgs::w_mx.
+static bool skinny_is_mxfp4(const c10::optional<at::Tensor>& w_scale) {
+  return w_scale && w_scale->scalar_type() == at::kByte;
+}
+
+static const unsigned char* skinny_mxfp4_scale(const at::Tensor& x, const at::Tensor& w,
+                                               const at::Tensor& w_scale, bool packed) {
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == at::kByte,
+              "skinny mxfp4: w must be packed uint8 nibbles when w_scale is uint8");
+  const int64_t N = w.size(0), K = x.size(1);
+  TORCH_CHECK(packed && K % 256 == 0 && N % 16 == 0 && K == 2 * w.size(1),
+              "skinny mxfp4: only packed weights [N, K / 2] with K % 256 == 0, N % 16 == 0 "
+              "(ops/mxfp4_weights.py)");
+  TORCH_CHECK(w_scale.is_cuda() && w_scale.device() == w.device() && w_scale.is_contiguous() &&
+              w_scale.numel() == N * K / 32 && w_scale.numel() < ((int64_t)1 << 31),
+              "skinny mxfp4: w_scale must be contiguous uint8 with one entry per 32 weights "
+              "(fewer than 2^31: the kernels address the scale stream with 32 bits)");
+  check_vec_aligned(w_scale, "w_scale");
+  return w_scale.data_ptr<uint8_t>();
+}
+
 // x [M, K] @ w[N, K]^T -> [M, N]
 at::Tensor skinny_gemm(const at::Tensor& x, const at::Tensor& w, bool packed,
                        const c10::optional<at::Tensor>& w_scale) {
   check_gpu(x, "x");
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1), "skinny_gemm: shapes");
+  const bool mx = skinny_is_mxfp4(w_scale);
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == (mx ? 2 : 1) * w.size(1),
+              "skinny_gemm: shapes");
   TORCH_CHECK(x.is_contiguous() && w.is_contiguous(), "skinny_gemm: contiguous operands");
   TORCH_CHECK(w_scale || x.scalar_type() == w.scalar_type(), "skinny_gemm: dtype mismatch");
   const int dt = dtype_code(x);
@@ -715,7 +741,8 @@ at::Tensor skinny_gemm(const at::Tensor& x, const at::Tensor& w, bool packed,
   p.K = (int)K;
   p.ldy = N;
   p.packed = packed ? 1 : 0;
-  if (w_scale) p.w_scale = skinny_fp8_scale(x, w, *w_scale, packed);
+  if (mx) p.w_mx = skinny_mxfp4_scale(x, w, *w_scale, packed);
+  else if (w_scale) p.w_scale = skinny_fp8_scale(x, w, *w_scale, packed);
   ema::skinny_gemm_ex(p, 0, dt, cur_stream());
   return y;
 }
@@ -728,7 +755,9 @@ static ema::SkinnyArgs skinny_args(const at::Tensor& x, const at::Tensor& w,
                                    const c10::optional<at::Tensor>& norm_w, double eps,
                                    bool packed, const c10::optional<at::Tensor>& w_scale) {
   check_gpu(x, "x");
-  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == w.size(1), "skinny: shapes");
+  const bool mx = skinny_is_mxfp4(w_scale);
+  TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == (mx ? 2 : 1) * w.size(1),
+              "skinny: shapes");
   TORCH_CHECK(x.is_contiguous() && w.is_contiguous(), "skinny: contiguous operands");
   TORCH_CHECK(w_scale || x.scalar_type() == w.scalar_type(), "skinny: dtype mismatch");
   const int dt = dtype_code(x);
@@ -742,7 +771,8 @@ static ema::SkinnyArgs skinny_args(const at::Tensor& x, const at::Tensor& w,
   p.K = (int)x.size(1);
   TORCH_CHECK(!packed || p.K % 256 == 0, "skinny: packed weights need K % 256 == 0");
   p.packed = packed ? 1 : 0;
-  if (w_scale) p.w_scale = skinny_fp8_scale(x, w, *w_scale, packed);
+  if (mx) p.w_mx = skinny_mxfp4_scale(x, w, *w_scale, packed);
+  else if (w_scale) p.w_scale = skinny_fp8_scale(x, w, *w_scale, packed);
   if (norm_w) {
     TORCH_CHECK(norm_w->is_cuda() && norm_w->is_contiguous() && norm_w->numel() == p.K &&
                 norm_w->scalar_type() == x.scalar_type(), "skinny: norm weight must be [K], x dtype");

@@ -377,6 +377,11 @@ struct SkinnyArgs {
   // order: [N], GLU [2N] up rows then gate rows) multiplies the fp32 sums
   // before the epilogue's first rounding.  nullptr: the 16-bit paths.
   const float* w_scale;
+  // MXFP4 weight-only decode: non-null = w holds e2m1 nibbles in the packed
+  // MXFP4 layout ([N, K / 2] bytes) and w_mx the N K / 32 e8m0 block scales in
+  // stream order (ops/mxfp4_weights.py); the conversion applies them, the
+  // epilogues are those of the 16-bit forms.  nullptr: the other paths.
+  const unsigned char* w_mx;
   // EPI_QKV, FP8 KV cache: non-null = the caches hold e4m3fn bytes (c_ss / c_sb
   // in bytes) and kv_scale is fp32 [2, ng] (row 0: K, row 1: V); a k / v value
   // is stored as e4m3_rne(clamp(x / scale, +-448)).  nullptr: 16-bit caches.

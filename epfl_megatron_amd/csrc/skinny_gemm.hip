@@ -54,6 +54,17 @@
 // conversion) right before its two MFMAs, so the MFMAs, the k order and every
 // rounding are those of the 16-bit forms on the same values; the epilogues
 // multiply the reduced fp32 tile by the row scales before their first rounding.
+//
+// MXFP4 weights (p.w_mx != nullptr; W4 forms, packed 8-wave only): W is OCP
+// e2m1 with one e8m0 scale per 32 k of a W row (ops/mxfp4_weights.py): one
+// scale per (W row, k-step).  One lane's 16-B piece holds its 8 nibbles of FOUR
+// consecutive k-steps (a ring slot = one 1 KiB unit per wave, lane L at byte
+// 16 L, plus the dword of its row's 4 scale bytes from the scale stream; the
+// S % 4 leftover k-steps are 4-B pieces with one scale byte each).  Each dword
+// is expanded by four v_cvt_scalef32_pk_T_fp4 (two nibbles -> two scaled T
+// values, exact) right before its MFMAs: the MFMAs, the k order, the fp32 sums
+// and the unchanged epilogues are those of the 16-bit forms on the dequantised
+// weights.
 #include <cstdlib>
 #include <type_traits>
 
@@ -87,6 +98,39 @@ __device__ __forceinline__ typename fa::MT<T>::x8 fp8x8(int lo, int hi) {
   const f2 c2 = __builtin_amdgcn_cvt_pk_f32_fp8(hi, false), c3 = __builtin_amdgcn_cvt_pk_f32_fp8(hi, true);
   o[0] = (T)c0[0]; o[1] = (T)c0[1]; o[2] = (T)c1[0]; o[3] = (T)c1[1];
   o[4] = (T)c2[0]; o[5] = (T)c2[1]; o[6] = (T)c3[0]; o[7] = (T)c3[1];
+  return o;
+}
+
+// W4 ring slot: the lane's 8 e2m1 nibbles of each of four k-steps and the four
+// e8m0 bytes (byte h = k-step h) of its W row
+struct W4Slot {
+  i4 v;
+  int sc;
+};
+
+// 8 e2m1 nibbles (k order: byte 0 low, byte 0 high, byte 1 low, ...) times
+// 2^(e8m0 byte h of sc - 127) -> one A fragment of T.  The quantiser keeps
+// every product a normal number of T, so the conversion is exact and the byte
+// is never the zero / NaN encoding.
+template <typename T>
+__device__ __forceinline__ typename fa::MT<T>::x8 fp4x8(int v, int sc, int h) {
+  typename fa::MT<T>::x8 o;
+  const float s = __builtin_bit_cast(float, ((sc >> (8 * h)) & 0xff) << 23);
+  if constexpr (__is_same(T, bf16)) {
+    const auto c0 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, s, 0);
+    const auto c1 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, s, 1);
+    const auto c2 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, s, 2);
+    const auto c3 = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, s, 3);
+    o[0] = c0[0]; o[1] = c0[1]; o[2] = c1[0]; o[3] = c1[1];
+    o[4] = c2[0]; o[5] = c2[1]; o[6] = c3[0]; o[7] = c3[1];
+  } else {
+    const auto c0 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(v, s, 0);
+    const auto c1 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(v, s, 1);
+    const auto c2 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(v, s, 2);
+    const auto c3 = __builtin_amdgcn_cvt_scalef32_pk_f16_fp4(v, s, 3);
+    o[0] = c0[0]; o[1] = c0[1]; o[2] = c1[0]; o[3] = c1[1];
+    o[4] = c2[0]; o[5] = c2[1]; o[6] = c3[0]; o[7] = c3[1];
+  }
   return o;
 }
 
@@ -272,12 +316,16 @@ __device__ __forceinline__ void epilogue(const SkinnyArgs& p, int blk, const f4&
 // MB: 16-row blocks of X (1: M <= 16; 2: M <= 32 -- every W fragment feeds
 // one MFMA per row block, so the weight stream is read once for 32 rows).
 // W8: e4m3 weights, a ring slot = one 16-B piece = SPU = 2 k-steps.
-template <typename T, int WAVES, bool NORM, int EPI, int ACT, bool PACKED, int MB, bool W8 = false>
+// W4: MXFP4 weights, a ring slot = one 16-B piece + its scale dword = 4 k-steps.
+template <typename T, int WAVES, bool NORM, int EPI, int ACT, bool PACKED, int MB, bool W8 = false,
+          bool W4 = false>
 __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) {
   typedef typename fa::MT<T>::x8 x8;
-  typedef std::conditional_t<W8, i4, x8> wslot;
-  static_assert(!W8 || PACKED, "e4m3 weights come decode-packed only");
-  constexpr int SPU = W8 ? 2 : 1;  // k-steps per ring slot
+  typedef std::conditional_t<W4, W4Slot, std::conditional_t<W8, i4, x8>> wslot;
+  static_assert(!(W8 || W4) || PACKED, "e4m3 / MXFP4 weights come decode-packed only");
+  static_assert(!(W8 && W4), "one weight format");
+  constexpr bool WQ = W8 || W4;       // byte-addressed stream of multi-step pieces
+  constexpr int SPU = W4 ? 4 : W8 ? 2 : 1;  // k-steps per ring slot
   // (a 16-deep ring for one row block measured the same: fc2 K = 11008 at
   // 16 rows 23.2 vs 23.0 us, profiles/r4al_skinny_u16.txt)
   // two un-normed row blocks (fc2 at 17-32 rows, K = 11008: 43 k-steps per
@@ -287,7 +335,11 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) 
   // 16 steps (8 pieces = the 8 KiB per wave of the 16-bit ring) in flight; two
   // row blocks keep the 16-bit forms' step counts (their X fragments are the
   // register cost) in half the pieces
-  constexpr int U = MB == 2 && !NORM ? 14 : W8 && MB == 1 ? 2 * SKINNY_U : SKINNY_U;
+  // W4: whole four-step slots; one row block keeps the W8 forms' 16 steps (4
+  // pieces + 4 scale dwords), two un-normed row blocks 12 (K = 11008: 43 =
+  // 3 x 12 + 7) beside fewer X fragments than the 14 of the other forms
+  constexpr int U = W4 ? (MB == 1 ? 2 * SKINNY_U : NORM ? SKINNY_U : 12)
+                       : MB == 2 && !NORM ? 14 : W8 && MB == 1 ? 2 * SKINNY_U : SKINNY_U;
   constexpr int US = U / SPU;  // ring slots
   static_assert(U % SPU == 0, "ring slots hold whole pieces");
   __shared__ f4 part[WAVES][MB][64];
@@ -307,14 +359,26 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) 
                        : w + w_row<EPI>(blockIdx.x, r, N) * K + kbeg + kc;
   // W8: the (block, wave) stream is steps x 512 B; the piece of k-steps s, s + 1
   // (s even) at byte 512 s + 16 lane, an odd last step at 512 s + 8 lane
+  // W4: steps x 256 B; the piece of k-steps s .. s + 3 (s % 4 == 0) at byte
+  // 256 s + 16 lane, a leftover step at 256 s + 4 lane; the scale stream is
+  // steps x 16 B: the row's dword of a piece at 16 s + 4 r, a leftover step's
+  // byte at 16 s + r
+  constexpr int SB = W4 ? 256 : 512;  // stream bytes per k-step
   const unsigned char* w8 =
-      (const unsigned char*)p.w + ((int64_t)blockIdx.x * WAVES + wave) * steps * 512;
-  auto wload = [&](int s) -> wslot {  // ring slot holding k-step s (W8: s even, and s + 1)
-    if constexpr (W8) return __builtin_nontemporal_load(reinterpret_cast<const i4*>(w8 + 512 * s + 16 * lane));
+      (const unsigned char*)p.w + ((int64_t)blockIdx.x * WAVES + wave) * steps * SB;
+  const unsigned char* smx =
+      W4 ? p.w_mx + ((int64_t)blockIdx.x * WAVES + wave) * steps * 16 : nullptr;
+  auto wload = [&](int s) -> wslot {  // ring slot holding k-step s (W8 / W4: and the next 1 / 3)
+    if constexpr (W4)
+      return W4Slot{__builtin_nontemporal_load(reinterpret_cast<const i4*>(w8 + 256 * s + 16 * lane)),
+                    __builtin_nontemporal_load(reinterpret_cast<const int*>(smx + 16 * s + 4 * r))};
+    else if constexpr (W8)
+      return __builtin_nontemporal_load(reinterpret_cast<const i4*>(w8 + 512 * s + 16 * lane));
     else return __builtin_nontemporal_load(reinterpret_cast<const x8*>(wr + WS * s));
   };
   auto afrag = [&](const wslot& v, int h) -> x8 {  // A fragment of the slot's k-step h
-    if constexpr (W8) return fp8x8<T>(v[2 * h], v[2 * h + 1]);
+    if constexpr (W4) return fp4x8<T>(v.v[h], v.sc, h);
+    else if constexpr (W8) return fp8x8<T>(v[2 * h], v[2 * h + 1]);
     else return v;
   };
   bool xon[MB];
@@ -443,11 +507,28 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) 
   // (W8: up to U - 1 steps in US pieces; an odd last step is an 8-B piece)
   {
     const int s0 = nblk * U, left = steps - s0;
-    constexpr int UL = W8 ? US : U - 1;
+    constexpr int UL = WQ ? US : U - 1;
 #pragma unroll
     for (int u = 0; u < UL; ++u) {
       if (SPU * u < left) {
-        if constexpr (W8) {
+        if constexpr (W4) {
+          // a whole piece, or the stream's last 1-3 steps as 4-B pieces with a
+          // scale byte each (put where afrag reads step h's)
+          if (SPU * u + 3 < left) {
+            a[u] = wload(s0 + SPU * u);
+          } else {
+            W4Slot t{i4{0, 0, 0, 0}, 0};
+#pragma unroll
+            for (int h = 0; h < 3; ++h) {
+              if (SPU * u + h < left) {
+                const int s = s0 + SPU * u + h;
+                t.v[h] = __builtin_nontemporal_load(reinterpret_cast<const int*>(w8 + 256 * s + 4 * lane));
+                t.sc |= (int)__builtin_nontemporal_load(smx + 16 * s + r) << (8 * h);
+              }
+            }
+            a[u] = t;
+          }
+        } else if constexpr (W8) {
           if (SPU * u + 1 < left) {
             a[u] = wload(s0 + SPU * u);
           } else {
@@ -512,15 +593,20 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) 
 //     wave 0 runs the epilogue while the other waves stream the next block.
 // W8 (e4m3 weights): a ring slot is one 16-B piece = SPU = 2 k-steps; U counts
 // k-steps in flight as before, held in U / 2 slots.
+// W4 (MXFP4 weights): a ring slot is one 16-B piece and its scale dword = 4
+// k-steps; a full unit's slots are 1 KiB / 64 scale bytes apart, a half
+// unit's 512 B / 32.
 template <typename T, bool NORM, int EPI, int ACT, int STEPS, int U, bool PACKED, int MB,
-          bool W8 = false>
+          bool W8 = false, bool W4 = false>
 __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
   typedef typename fa::MT<T>::x8 x8;
-  typedef std::conditional_t<W8, i4, x8> wslot;
-  typedef std::conditional_t<W8, unsigned char, T> WT;  // W8: the stream is addressed in bytes
+  typedef std::conditional_t<W4, W4Slot, std::conditional_t<W8, i4, x8>> wslot;
+  constexpr bool WQ = W8 || W4;
+  typedef std::conditional_t<WQ, unsigned char, T> WT;  // W8 / W4: the stream is addressed in bytes
   constexpr int WAVES = 8;
-  constexpr int SPU = W8 ? 2 : 1, US = U / SPU, SLOTS = STEPS / SPU;
-  static_assert(!W8 || PACKED, "e4m3 weights come decode-packed only");
+  constexpr int SPU = W4 ? 4 : W8 ? 2 : 1, US = U / SPU, SLOTS = STEPS / SPU;
+  static_assert(!WQ || PACKED, "e4m3 / MXFP4 weights come decode-packed only");
+  static_assert(!(W8 && W4), "one weight format");
   static_assert(STEPS % U == 0 && U % SPU == 0, "ring must tile the k-steps");
   static_assert(!NORM || STEPS == 16, "the normed forms keep 64 gamma chunks per wave");
   static_assert(MB == 1 || STEPS == 16, "two row blocks keep 2 x 16 X fragments in registers");
@@ -555,10 +641,17 @@ __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
   auto unit_half = [&](int j) { return j < rounds || !halves ? -1 : (wg & 1); };
   // elements between a lane's consecutive k-steps of unit j (W8: bytes
   // between its consecutive 16-B pieces: a 1 KiB / 512 B unit per two k-steps)
-  auto wstr = [&](int j) { return !PACKED ? 32 : unit_half(j) < 0 ? 512 * SPU : 256 * SPU; };
+  constexpr int SLOTB = W4 ? 1024 : 512 * SPU;
+  auto wstr = [&](int j) { return !PACKED ? 32 : unit_half(j) < 0 ? SLOTB : SLOTB / 2; };
   auto wptr = [&](int j) {
     const int b = unit_blk(j), h = unit_half(j);
-    if constexpr (W8) {
+    if constexpr (W4) {
+      // the same order at 4 bits per weight
+      if (h < 0) return w + ((int64_t)b * WAVES + wave) * STEPS * 256 + 16 * lane;
+      const int64_t tail = (int64_t)(nblocks - nrem) * 8 * K;
+      const int unit = (b - (nblocks - nrem)) * 2 + h, pr = (r & 3) + 4 * (r >> 3);
+      return w + tail + ((int64_t)unit * WAVES + wave) * STEPS * 128 + 16 * (kc + pr);
+    } else if constexpr (W8) {
       // the same (block, wave) / (half unit, wave) order as the 16-bit pack at
       // 1 B per weight; lane L's piece at byte 16 L, in a half unit at 16 (kc + pr)
       if (h < 0) return w + ((int64_t)b * WAVES + wave) * STEPS * 512 + 16 * lane;
@@ -577,9 +670,28 @@ __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
       return w + row * K + kbeg + kc;
     }
   };
+  // W4: the scale dword of the lane's W row for the first slot of unit j (16
+  // scale bytes per row block and k-step, 8 in a half unit) and the bytes
+  // between consecutive slots' dwords
+  auto sstr = [&](int j) { return unit_half(j) < 0 ? 64 : 32; };
+  // (byte offsets into the scale stream: N K / 32 < 2^31, checked by the host)
+  auto sptr = [&](int j) -> unsigned {
+    const int b = unit_blk(j), h = unit_half(j);
+    if (h < 0) return (unsigned)((b * WAVES + wave) * STEPS * 16 + 4 * r);
+    const unsigned tail = (unsigned)(nblocks - nrem) * (unsigned)(K / 2);
+    const int unit = (b - (nblocks - nrem)) * 2 + h, pr = (r & 3) + 4 * (r >> 3);
+    return tail + (unsigned)((unit * WAVES + wave) * STEPS * 8 + 4 * pr);
+  };
   auto afrag = [&](const wslot& v, int h) -> x8 {  // A fragment of the slot's k-step h
-    if constexpr (W8) return fp8x8<T>(v[2 * h], v[2 * h + 1]);
+    if constexpr (W4) return fp4x8<T>(v.v[h], v.sc, h);
+    else if constexpr (W8) return fp8x8<T>(v[2 * h], v[2 * h + 1]);
     else return v;
+  };
+  auto sload = [&](const WT* wp, unsigned so) -> wslot {  // one ring slot
+    if constexpr (W4)
+      return W4Slot{__builtin_nontemporal_load(reinterpret_cast<const i4*>(wp)),
+                    __builtin_nontemporal_load(reinterpret_cast<const int*>(p.w_mx + so))};
+    else return __builtin_nontemporal_load(reinterpret_cast<const wslot*>(wp));
   };
   int j = 0, blk = unit_blk(0), half = unit_half(0);
   EpiPre<T, EPI> pre[MB];  // wave 0: the epilogue operands of the current block
@@ -594,10 +706,21 @@ __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
   // W8: where no unit follows, the ring's refills past the unit's end read one
   // 16-B line of the scales (every lane the same address, stride 0; never
   // used) instead of fetching a unit's first pieces a second time
-  const WT* wdummy = (const WT*)p.w_scale;
+  // (W4: of the scale stream, for the pieces and the scale dwords alike)
+  const WT* wdummy = W4 ? (const WT*)p.w_mx : (const WT*)p.w_scale;
   const WT* wr = wptr(0);
-  const WT* wn = W8 && nunits <= 1 ? wdummy : wptr(nunits > 1 ? 1 : 0);
-  int ws = wstr(0), wsn = W8 && nunits <= 1 ? 0 : wstr(nunits > 1 ? 1 : 0);
+  const WT* wn = WQ && nunits <= 1 ? wdummy : wptr(nunits > 1 ? 1 : 0);
+  int ws = wstr(0), wsn = WQ && nunits <= 1 ? 0 : wstr(nunits > 1 ? 1 : 0);
+  unsigned sr = 0, sn = 0;  // W4: the scale dwords of the current / next unit
+  int ss = 0, ssn = 0;
+  auto sinit = [&] {
+    if constexpr (W4) {
+      sr = sptr(0);
+      ss = sstr(0);
+      sn = nunits <= 1 ? 0 : sptr(1);
+      ssn = nunits <= 1 ? 0 : sstr(1);
+    }
+  };
 
   // X (and gamma) first, the weight ring right behind them: a wave's loads
   // return in order, so X lands first and the norm prologue runs while the
@@ -628,9 +751,13 @@ __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
   // the un-normed forms instead (models/transformer.py _forward_decode_fused;
   // profiles/r4ai_skinny_mb.txt, r4aj_skinny_mb.txt).
   constexpr bool RING_FIRST = !(NORM && MB == 2);
+  // (bf16, two normed row blocks: after the norm prologue, where these forms
+  // spill in every weight format; profiles/r14a_mxfp4_isa.txt)
+  constexpr bool SCALES_LATE = !RING_FIRST && __is_same(T, bf16);
+  if constexpr (!SCALES_LATE) sinit();
   if constexpr (RING_FIRST) {
 #pragma unroll
-    for (int u = 0; u < US; ++u) a[u] = __builtin_nontemporal_load(reinterpret_cast<const wslot*>(wr + ws * u));
+    for (int u = 0; u < US; ++u) a[u] = sload(wr + ws * u, sr + ss * u);
   }
   if constexpr (NORM) {
 #pragma unroll
@@ -671,8 +798,9 @@ __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
   }
 
   if constexpr (!RING_FIRST) {
+    if constexpr (SCALES_LATE) sinit();
 #pragma unroll
-    for (int u = 0; u < US; ++u) a[u] = __builtin_nontemporal_load(reinterpret_cast<const wslot*>(wr + ws * u));
+    for (int u = 0; u < US; ++u) a[u] = sload(wr + ws * u, sr + ss * u);
   }
 
   // one block's k-steps; LAST: the workgroup's final block, whose last U
@@ -701,7 +829,8 @@ __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
       }
       if (!LAST || s + US < SLOTS) {
         const WT* src = s + US < SLOTS ? wr + ws * (s + US) : wn + wsn * (s + US - SLOTS);
-        a[s % US] = __builtin_nontemporal_load(reinterpret_cast<const wslot*>(src));
+        const unsigned ssrc = s + US < SLOTS ? sr + ss * (s + US) : sn + ssn * (s + US - SLOTS);
+        a[s % US] = sload(src, ssrc);
       }
       __builtin_amdgcn_sched_barrier(0);  // {MFMA s, refill s} in program order
     }
@@ -710,7 +839,7 @@ __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
   for (;; ++j) {
     const bool last = j + 1 >= nunits;
     Acc acc;
-    if constexpr (W8) acc = run_block(std::false_type{});
+    if constexpr (WQ) acc = run_block(std::false_type{});
     else acc = last ? run_block(std::true_type{}) : run_block(std::false_type{});
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) part[j & 1][wave][mb][lane] = acc.v[mb];
@@ -737,8 +866,14 @@ __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
     }
     wr = wn;
     ws = wsn;
-    wn = W8 && j + 2 >= nunits ? wdummy : wptr(j + 2 < nunits ? j + 2 : nunits - 1);
-    wsn = W8 && j + 2 >= nunits ? 0 : wstr(j + 2 < nunits ? j + 2 : nunits - 1);
+    wn = WQ && j + 2 >= nunits ? wdummy : wptr(j + 2 < nunits ? j + 2 : nunits - 1);
+    wsn = WQ && j + 2 >= nunits ? 0 : wstr(j + 2 < nunits ? j + 2 : nunits - 1);
+    if constexpr (W4) {
+      sr = sn;
+      ss = ssn;
+      sn = j + 2 >= nunits ? 0 : sptr(j + 2);
+      ssn = j + 2 >= nunits ? 0 : sstr(j + 2);
+    }
   }
 }
 
@@ -759,6 +894,31 @@ template <typename T, int WAVES, int STEPS, bool NORM, int EPI, int ACT>
 void launch(const SkinnyArgs& p, hipStream_t s) {
   const int nblocks = EPI == EPI_GLU ? p.N / 8 : p.N / 16;
   if constexpr (WAVES == 8) {
+    if (p.w_mx) {  // MXFP4 weights: packed 8-wave forms only (checked by the host)
+      if constexpr (STEPS == 0) {
+        if (p.M > 16)
+          hipLaunchKernelGGL((skinny_gemm_k<T, 8, NORM, EPI, ACT, true, 2, false, true>),
+                             dim3((unsigned)nblocks), dim3(512), 0, s, p);
+        else
+          hipLaunchKernelGGL((skinny_gemm_k<T, 8, NORM, EPI, ACT, true, 1, false, true>),
+                             dim3((unsigned)nblocks), dim3(512), 0, s, p);
+      } else {
+        // the ring holds one whole unit: 4 / 8 pieces (+ scale dwords) per wave at
+        // K = 4096 / 8192, at most the register ring of the W8 forms (two normed
+        // row blocks, whose bf16 forms spill in every weight format: 2 pieces, with
+        // which they spill less than their W8 twins; the decode layer does not
+        // call them)
+        const int g = nblocks < num_cus() ? nblocks : num_cus();
+        if (STEPS == 16 && p.M > 16)
+          hipLaunchKernelGGL((skinny_pgemm_k<T, NORM, EPI, ACT, STEPS, NORM ? 8 : STEPS, true,
+                                             STEPS == 16 ? 2 : 1, false, true>),
+                             dim3((unsigned)g), dim3(512), 0, s, p);
+        else
+          hipLaunchKernelGGL((skinny_pgemm_k<T, NORM, EPI, ACT, STEPS, STEPS, true, 1, false, true>),
+                             dim3((unsigned)g), dim3(512), 0, s, p);
+      }
+      return;
+    }
     if (p.w_scale) {  // e4m3 weights: packed 8-wave forms only (checked by the host)
       if constexpr (STEPS == 0) {
         if (p.M > 16)

@@ -37,7 +37,7 @@ from ..ops._ext import use_native, ext
 from ..parallel.context import chunk_position_ids, ring_attention
 from ..ops.attention import flash_attn_qkvpacked, flash_attn_func, flash_decode_cached
 from ..ops.activations import glu, bias_gelu, gelu
-from ..ops import decode_pack, fp8_kv, fp8_weights
+from ..ops import decode_pack, fp8_kv, fp8_weights, mxfp4_weights
 from ..ops.softmax import FusedScaleMaskSoftmax
 from .enums import AttnMaskType, AttnType, LayerType, ModelType, PositionEmbeddingType
 from .module import MegatronModule
@@ -61,6 +61,18 @@ def set_fp8_weights(on):
     """Switch FP8 weight-only decode for every fused decode layer of the process."""
     global _FP8_WEIGHTS
     _FP8_WEIGHTS = bool(on)
+
+
+# MXFP4 weight-only decode (--inference_mxfp4_weights, opt-in; excludes the FP8
+# weights): the same four products stream e2m1 nibbles with one e8m0 scale per
+# 32 weights along K (ops/mxfp4_weights.py).
+_MXFP4_WEIGHTS = os.environ.get("EMA_MXFP4_WEIGHTS", "0") == "1"
+
+
+def set_mxfp4_weights(on):
+    """Switch MXFP4 weight-only decode for every fused decode layer of the process."""
+    global _MXFP4_WEIGHTS
+    _MXFP4_WEIGHTS = bool(on)
 
 
 # FP8 KV cache (--inference_fp8_kv_cache, opt-in): caches allocated under the
@@ -632,11 +644,17 @@ class ParallelTransformerLayer(MegatronModule):
         tail = C.skinny_glu_half_tail(w1.shape[0] // 2, w1.shape[1], not sep, b)
 
         def stream(w, **form):
-            """(weight to stream, its e4m3 row scales or None): the FP8 pair
-            under --inference_fp8_weights where the shape packs (each TP rank
-            quantises its own shard; a row-parallel partial sum is scaled
-            before the all-reduce), else the 16-bit pack or None."""
-            pair = fp8_weights.packed_fp8(w, **form) if _FP8_WEIGHTS else None
+            """(weight to stream, its e4m3 row scales / e8m0 block scales or
+            None): the MXFP4 pair under --inference_mxfp4_weights or the FP8
+            pair under --inference_fp8_weights where the shape packs (each TP
+            rank quantises its own shard: an FP8 row-parallel partial sum is
+            scaled before the all-reduce, and the MXFP4 blocks run along K,
+            which a row-parallel shard cuts at multiples of 256), else the
+            16-bit pack or None."""
+            if _MXFP4_WEIGHTS:
+                pair = mxfp4_weights.packed_mxfp4(w, **form)
+            else:
+                pair = fp8_weights.packed_fp8(w, **form) if _FP8_WEIGHTS else None
             return pair if pair is not None else (decode_pack.packed(w, **form), None)
         (pq, sq), (po, so) = stream(wq), stream(wo)
         (p1, s1), (p2, s2) = stream(w1, glu=True, half_tail=tail), stream(w2)
@@ -783,6 +801,8 @@ class ParallelTransformer(MegatronModule):
         super().__init__()
         if getattr(args, "inference_fp8_weights", False):
             set_fp8_weights(True)
+        if getattr(args, "inference_mxfp4_weights", False):
+            set_mxfp4_weights(True)
         if getattr(args, "inference_fp8_kv_cache", False):
             set_fp8_kv_cache(True, calibrate=bool(getattr(args, "inference_fp8_kv_calibrate",
                                                           False)) or None)

@@ -40,6 +40,8 @@ def main():
                     help="without --graph: sample with inference/sampling.py's eager chain")
     ap.add_argument("--fp8_weights", action="store_true",
                     help="FP8 weight-only decode (--inference_fp8_weights; ops/fp8_weights.py)")
+    ap.add_argument("--mxfp4_weights", action="store_true",
+                    help="MXFP4 weight-only decode (--inference_mxfp4_weights; ops/mxfp4_weights.py)")
     ap.add_argument("--fp8_kv_cache", action="store_true",
                     help="FP8 KV cache (--inference_fp8_kv_cache; ops/fp8_kv.py)")
     a = ap.parse_args()
@@ -75,6 +77,8 @@ def main():
             "--global_batch_size", "1", "--train_iters", "1", "--lr", "1e-4"]
     if a.fp8_weights:
         argv.append("--inference_fp8_weights")
+    if a.mxfp4_weights:
+        argv.append("--inference_mxfp4_weights")
     if a.fp8_kv_cache:
         argv.append("--inference_fp8_kv_cache")
     initialize_megatron(finetune.extra_args, {"tokenizer_type": "NullTokenizer"}, args_list=argv)
