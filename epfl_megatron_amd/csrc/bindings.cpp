@@ -837,7 +837,8 @@ static const float* kv_scale_ptr(const at::Tensor& sc, int64_t nkv, const at::Te
 
 // Quantising store of k / v [sq, b, nkv, hd] (bf16 / fp16, hd contiguous) into
 // rows slot .. slot + sq - 1 of the e4m3 caches [L, B, nkv, hd] (uint8 views at
-// the batch offset); slot from `slot_t` (int64 device scalar) when given.
+// the batch offset); slot from `slot_t` (int64 device scalar) when given, or
+// with sq == 1 and b > 1 elements one slot per sequence.
 void kv_store_fp8(const at::Tensor& k, const at::Tensor& v, at::Tensor kcache, at::Tensor vcache,
                   const at::Tensor& kv_scale, const c10::optional<at::Tensor>& slot_t,
                   int64_t slot) {
@@ -869,6 +870,8 @@ void kv_store_fp8(const at::Tensor& k, const at::Tensor& v, at::Tensor kcache, a
                 "kv store: slot int64");
     TORCH_CHECK(sq <= kcache.size(0), "kv store: more rows than the cache holds");
     p.slot_ptr = slot_t->data_ptr<int64_t>();
+    // one slot per sequence (ragged decode) when there is one element per row
+    p.slot_sb = (sq == 1 && b > 1 && slot_t->numel() == b && slot_t->is_contiguous()) ? 1 : 0;
   } else {
     TORCH_CHECK(slot >= 0 && slot + sq <= kcache.size(0), "kv store: slot out of range");
     p.slot = slot;
@@ -884,7 +887,7 @@ void kv_store_fp8(const at::Tensor& k, const at::Tensor& v, at::Tensor kcache, a
 
 // qkv decode projection: returns the rotated q [M, ng * r * hd]; k / v rows go
 // to kcache / vcache [L, B, ng, hd] (views at the batch offset) at the slot
-// `slot_t` (int64 device scalar) or `slot`.
+// `slot_t` (int64 device scalar, or M > 1 elements: row m's slot) or `slot`.
 at::Tensor skinny_qkv_rope_cache(const at::Tensor& x, const at::Tensor& w,
                                  const c10::optional<at::Tensor>& norm_w, double eps, int64_t ng,
                                  int64_t r, int64_t hd, const at::Tensor& cos,
@@ -915,8 +918,11 @@ at::Tensor skinny_qkv_rope_cache(const at::Tensor& x, const at::Tensor& w,
   TORCH_CHECK(kcache.stride(0) == vcache.stride(0) && kcache.stride(1) == vcache.stride(1),
               "skinny qkv: k / v cache strides differ");
   if (slot_t) {
-    TORCH_CHECK(slot_t->is_cuda() && slot_t->scalar_type() == at::kLong, "skinny qkv: slot int64");
+    TORCH_CHECK(slot_t->is_cuda() && slot_t->scalar_type() == at::kLong && slot_t->numel() >= 1,
+                "skinny qkv: slot int64");
     p.slot_ptr = slot_t->data_ptr<int64_t>();
+    // one slot per row (ragged decode) when there is one element per row
+    p.slot_sb = (p.M > 1 && slot_t->numel() == p.M && slot_t->is_contiguous()) ? 1 : 0;
   } else {
     TORCH_CHECK(slot >= 0 && slot < kcache.size(0), "skinny qkv: slot out of range");
     p.slot = slot;
@@ -990,6 +996,8 @@ void flash_decode(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
   p.o_sb = os[0]; p.o_sh = os[2];
   p.scale = (float)scale;
   p.kv_len = kv_len ? kv_len->data_ptr<int>() : nullptr;
+  // one length per sequence (ragged decode) when there is one element per row
+  p.kv_len_sb = (kv_len && b > 1 && kv_len->numel() == b && kv_len->is_contiguous()) ? 1 : 0;
   if (kv8) {
     p.kv_fp8 = 1;
     p.k_scale = kv_scale_ptr(*kv_scale, nkv, q);
@@ -1091,6 +1099,40 @@ void sample_tail(const at::Tensor& logits, at::Tensor tokens, at::Tensor history
                    slot.data_ptr<int64_t>(), kv_len.data_ptr<int>(),
                    reinterpret_cast<unsigned*>(counter.data_ptr<int>()), ctl.data_ptr<int64_t>(),
                    fctl.data_ptr<float>(), ema::SampleArgs{}, cur_stream());
+}
+
+// Ragged tails (inference/continuous.py): per-row state hist_idx / slot / pos /
+// limit int64 [b], kv_len / active int32 [b], tick int64 [1]; ctl / fctl as in
+// sample_tail (the greedy form, sample == false, reads only ctl[4] = stop_id);
+// ctl[5] receives the number of rows still active.
+void ragged_tail(const at::Tensor& logits, at::Tensor tokens, at::Tensor history,
+                 at::Tensor hist_idx, at::Tensor pos, at::Tensor slot, at::Tensor kv_len,
+                 at::Tensor active, at::Tensor limit, at::Tensor tick, at::Tensor counter,
+                 at::Tensor ctl, at::Tensor fctl, bool sample) {
+  const int dt = check_sample_logits(logits, "ragged_tail");
+  const int64_t b = logits.size(0), V = logits.size(1);
+  for (const at::Tensor* t : {&tokens, &hist_idx, &pos, &slot, &limit})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kLong && t->is_contiguous() &&
+                    t->numel() == b, "ragged_tail: int64 [b] state tensors");
+  for (const at::Tensor* t : {&kv_len, &active})
+    TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kInt && t->is_contiguous() &&
+                    t->numel() == b, "ragged_tail: kv_len / active int32 [b]");
+  TORCH_CHECK(history.is_cuda() && history.scalar_type() == at::kLong && history.dim() == 2 &&
+                  history.size(0) == b && history.stride(1) == 1, "ragged_tail: history int64 [b, H]");
+  TORCH_CHECK(tick.is_cuda() && tick.scalar_type() == at::kLong && tick.numel() == 1 &&
+                  counter.is_cuda() && counter.scalar_type() == at::kInt && counter.numel() >= 1,
+              "ragged_tail: tick int64 [1], counter int32 [1]");
+  TORCH_CHECK(ctl.is_cuda() && ctl.scalar_type() == at::kLong && ctl.is_contiguous() &&
+                  ctl.numel() == 6 && fctl.is_cuda() && fctl.scalar_type() == at::kFloat &&
+                  fctl.is_contiguous() && fctl.numel() == 2,
+              "ragged_tail: ctl int64 [6], fctl float32 [2]");
+  ema::RaggedTail st{hist_idx.data_ptr<int64_t>(), slot.data_ptr<int64_t>(), kv_len.data_ptr<int>(),
+                     pos.data_ptr<int64_t>(), active.data_ptr<int>(), limit.data_ptr<int64_t>(),
+                     tick.data_ptr<int64_t>()};
+  ema::ragged_tail(logits.data_ptr(), logits.stride(0), (int)V, (int)b, dt, sample,
+                   tokens.data_ptr<int64_t>(), history.data_ptr<int64_t>(), history.stride(0),
+                   history.size(1), st, reinterpret_cast<unsigned*>(counter.data_ptr<int>()),
+                   ctl.data_ptr<int64_t>(), fctl.data_ptr<float>(), cur_stream());
 }
 
 // One draw per row of logits [b, V] into tokens int64 [b]; no tail state, the
@@ -1484,6 +1526,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("fa_set_kv2", &ema::fa_set_kv2);
   m.def("greedy_tail", &greedy_tail);
   m.def("sample_tail", &sample_tail);
+  m.def("ragged_tail", &ragged_tail, py::arg("logits"), py::arg("tokens"), py::arg("history"),
+        py::arg("hist_idx"), py::arg("pos"), py::arg("slot"), py::arg("kv_len"), py::arg("active"),
+        py::arg("limit"), py::arg("tick"), py::arg("counter"), py::arg("ctl"), py::arg("fctl"),
+        py::arg("sample") = false);
   m.def("sample_rows", &sample_rows, py::arg("logits"), py::arg("tokens"), py::arg("seed"),
         py::arg("offset"), py::arg("top_k"), py::arg("top_p"), py::arg("temperature"),
         py::arg("vocab_limit"));

@@ -5,6 +5,13 @@
 // the step index, the KV-cache slot and the valid-key count.  The eager form
 // was seven launches (argmax, index_copy, copy, four adds: ~45 us per token at
 // batch 1 with their graph seams, profiles/r4v_decode_b1_kernels.txt).
+// sample_tail_k: the same with a temperature / top-k / top-p draw.  Both move
+// the batch in lockstep: one step index, cache slot and key count for all rows.
+// ragged_tail_k (inference/continuous.py) is the tail of a batch of independent
+// sequences: history index, cache slot, key count, position, limit and an
+// active flag per row, so a finished row parks and can be refilled between
+// replays of the same graph.  The selection code (argmax_row, draw_row) is
+// shared; only thread 0's bookkeeping differs.
 //
 // Reference: megatron/text_generation/generation.py:179-264 samples on the
 // host-driven loop (greedy = argmax of the last position's logits).
@@ -38,16 +45,13 @@ __device__ __forceinline__ void take(float& bv, int& bi, float v, int i) {
   }
 }
 
+// argmax of one row over the 1024 threads of a workgroup: the result is valid
+// in thread 0 (shared by greedy_tail_k and the ragged tail)
 template <typename T>
-__global__ __launch_bounds__(1024) void greedy_tail_k(const T* __restrict__ logits, int64_t ld, int V,
-                                                     int64_t* tokens, int64_t* history,
-                                                     int64_t hist_ld, int64_t* step_idx,
-                                                     int64_t* pos, int64_t* slot, int* kv_len,
-                                                     unsigned* counter) {
+__device__ __forceinline__ int argmax_row(const T* __restrict__ lr, int V, int tid) {
   typedef typename Vec16<T>::t vec;
   constexpr int NV = Vec16<T>::n;
-  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const T* lr = logits + (int64_t)row * ld;
+  const int lane = tid & 63, wave = tid >> 6;
   float bv = -INFINITY;
   int bi = 0x7fffffff;
   // 16-B loads, 8 in flight per thread per round over 1024 threads (one
@@ -86,9 +90,22 @@ __global__ __launch_bounds__(1024) void greedy_tail_k(const T* __restrict__ logi
     si[wave] = bi;
   }
   __syncthreads();
-  if (tid != 0) return;
+  if (tid == 0) {
 #pragma unroll
-  for (int w = 1; w < NT / 64; ++w) take(bv, bi, sv[w], si[w]);
+    for (int w = 1; w < NT / 64; ++w) take(bv, bi, sv[w], si[w]);
+  }
+  return bi;
+}
+
+template <typename T>
+__global__ __launch_bounds__(1024) void greedy_tail_k(const T* __restrict__ logits, int64_t ld, int V,
+                                                     int64_t* tokens, int64_t* history,
+                                                     int64_t hist_ld, int64_t* step_idx,
+                                                     int64_t* pos, int64_t* slot, int* kv_len,
+                                                     unsigned* counter) {
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const int bi = argmax_row<T>(logits + (int64_t)row * ld, V, tid);
+  if (tid != 0) return;
   const int64_t s = *step_idx;
   tokens[row] = bi;
   history[(int64_t)row * hist_ld + s] = bi;
@@ -200,16 +217,14 @@ __device__ __forceinline__ void row_for_each(const T* __restrict__ lr, int V, in
   for (int i = nvec * NV + tid; i < V; i += ST_NT) f((float)lr[i], i);
 }
 
+// The draw of one row (the filters and the Gumbel-max of the comment above, or
+// the plain argmax at top_k == 1) over the 1024 threads of a workgroup, noise
+// at Philox offset a.offset0 + step: the token is valid in thread 0, before the
+// vocab_limit clamp (shared by sample_tail_k and the ragged tail)
 template <typename T>
-__global__ __launch_bounds__(1024) void sample_tail_k(const T* __restrict__ logits, int64_t ld, int V,
-                                                     int64_t* tokens, int64_t* history,
-                                                     int64_t hist_ld, int64_t hist_cols,
-                                                     int64_t* step_idx, int64_t* pos,
-                                                     int64_t* slot, int* kv_len, unsigned* counter,
-                                                     int64_t* ctl, const float* fctl,
-                                                     SampleArgs a) {
-  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const T* lr = logits + (int64_t)row * ld;
+__device__ __forceinline__ int draw_row(const T* __restrict__ lr, int V, int row, int tid,
+                                        const SampleArgs& a, int64_t step) {
+  const int lane = tid & 63, wave = tid >> 6;
   __shared__ u64 hist[ST_NB];
   __shared__ u64 swt[ST_NT / 64];
   __shared__ u64 ssel[2];
@@ -218,6 +233,166 @@ __global__ __launch_bounds__(1024) void sample_tail_k(const T* __restrict__ logi
   __shared__ unsigned ncand;
   __shared__ float sv[ST_NT / 64];
   __shared__ int si[ST_NT / 64];
+  float bv = -INFINITY;
+  int bi = 0x7fffffff;
+  if (a.top_k == 1) {
+    row_for_each<T>(lr, V, tid, [&](float x, int i) { take(bv, bi, x, i); });
+  } else {
+    const float temp = a.temperature;
+    const bool topk = a.top_k > 1, topp = !topk && a.top_p > 0.f;
+    uint32_t kstar = 0;
+    const uint64_t off = (uint64_t)(a.offset0 + step), seed = (uint64_t)a.seed;
+    const uint64_t chi = (uint64_t)row << 32;
+    auto draw = [&](float y, int i) {
+      const U4 r = philox(chi | (uint32_t)(i >> 2), off, seed);
+      const int q = i & 3;
+      const uint32_t w = q == 0 ? r.x : q == 1 ? r.y : q == 2 ? r.z : r.w;
+      take(bv, bi, y + gumbel(w), i);
+    };
+    if (!(topk || topp)) {
+      row_for_each<T>(lr, V, tid, [&](float x, int i) { draw(tempered(x, temp), i); });
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) hist[4 * tid + j] = 0;
+      if (tid == 0) ncand = 0;
+      float m = 0.f;
+      if (topp) {
+        float lm = -INFINITY;
+        row_for_each<T>(lr, V, tid, [&](float x, int) { lm = fmaxf(lm, tempered(x, temp)); });
+        m = block_max(lm, sv);
+      }
+      __syncthreads();
+      u64 carry = 0, budget = topk ? (u64)(a.top_k - 1) : 0;
+      unsigned nlist = 0;
+      bool in_list = false;  // the threshold bin's elements are in ckey / cidx
+      for (int p = 0; p < 3; ++p) {
+        const int shift = p == 0 ? 20 : p == 1 ? 10 : 0;
+        const int bits = p == 0 ? 12 : 10;
+        const uint32_t prefix = kstar;
+        auto add = [&](float y, uint32_t k) {
+          if (p == 0 || (k >> (shift + bits)) == prefix) {
+            u64 w = 1;
+            // fixed-point softmax numerator, exp(y - max) * 2^40 <= 2^40:
+            // V <= 2^22 of them sum below 2^63 (hardware exp2: the argument's
+            // rounding is < 3e-6 relative at y - max = -30, where the mass is nil)
+            if (topp) w = y == -INFINITY ? 0 : (u64)(__expf(y - m) * 0x1p40f);
+            atomicAdd(&hist[(k >> shift) & ((1u << bits) - 1u)], w);
+          }
+        };
+        if (in_list) {
+          for (unsigned c = tid; c < nlist; c += ST_NT) add(unkey(ckey[c]), ckey[c]);
+        } else {
+          row_for_each<T>(lr, V, tid, [&](float x, int) {
+            const float y = tempered(x, temp);
+            add(y, okey(y));
+          });
+        }
+        __syncthreads();
+        u64 h[4], loc = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          h[j] = hist[4 * tid + j];
+          hist[4 * tid + j] = 0;
+          loc += h[j];
+        }
+        // inclusive suffix sum over the 1024 threads (integers: exact)
+        u64 incl = loc;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const u64 t = __shfl_down(incl, o, 64);
+          if (lane + o < 64) incl += t;
+        }
+        if (lane == 0) swt[wave] = incl;
+        __syncthreads();
+        u64 after = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < ST_NT / 64; ++w) {
+          const u64 v = swt[w];
+          total += v;
+          if (w > wave) after += v;
+        }
+        if (p == 0 && topp)
+          budget = a.top_p >= 1.f ? total : (u64)((double)a.top_p * (double)total);
+        // above[j]: weight strictly above bin 4 tid + j; the digit is the
+        // smallest bin with above <= budget (exactly one bin qualifies)
+        u64 above = carry + after + (incl - loc);
+#pragma unroll
+        for (int j = 3; j >= 0; --j) {
+          const u64 below = above + h[j];  // weight above bin 4 tid + j - 1
+          if (above <= budget && (below > budget || 4 * tid + j == 0)) {
+            ssel[0] = (u64)(4 * tid + j);
+            ssel[1] = above;
+          }
+          above = below;
+        }
+        __syncthreads();
+        kstar = (kstar << bits) | (uint32_t)ssel[0];
+        carry = ssel[1];
+        if (p == 0) {
+          // the first digit d of K* is known: every element of a bin above d
+          // is kept and drawn now; bin d's (key, index) go to an LDS list,
+          // from which the two lower digits and the last draws are taken
+          // (the row is read again for them only if the list overflows)
+          const uint32_t d = kstar;
+          row_for_each<T>(lr, V, tid, [&](float x, int i) {
+            const float y = tempered(x, temp);
+            const uint32_t k = okey(y);
+            if ((k >> 20) > d) {
+              draw(y, i);
+            } else if ((k >> 20) == d) {
+              const unsigned c = atomicAdd(&ncand, 1u);
+              if (c < ST_CAP) {
+                ckey[c] = k;
+                cidx[c] = i;
+              }
+            }
+          });
+          __syncthreads();
+          nlist = ncand;
+          in_list = nlist <= ST_CAP;
+        }
+      }
+      if (in_list) {
+        for (unsigned c = tid; c < nlist; c += ST_NT)
+          if (ckey[c] >= kstar) draw(unkey(ckey[c]), cidx[c]);
+      } else {
+        row_for_each<T>(lr, V, tid, [&](float x, int i) {
+          const float y = tempered(x, temp);
+          const uint32_t k = okey(y);
+          if ((k >> 20) == (kstar >> 20) && k >= kstar) draw(y, i);
+        });
+      }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    take(bv, bi, ov, oi);
+  }
+  __syncthreads();
+  if (lane == 0) {
+    sv[wave] = bv;
+    si[wave] = bi;
+  }
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int w = 1; w < ST_NT / 64; ++w) take(bv, bi, sv[w], si[w]);
+  }
+  return bi;
+}
+
+template <typename T>
+__global__ __launch_bounds__(1024) void sample_tail_k(const T* __restrict__ logits, int64_t ld, int V,
+                                                     int64_t* tokens, int64_t* history,
+                                                     int64_t hist_ld, int64_t hist_cols,
+                                                     int64_t* step_idx, int64_t* pos,
+                                                     int64_t* slot, int* kv_len, unsigned* counter,
+                                                     int64_t* ctl, const float* fctl,
+                                                     SampleArgs a) {
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const T* lr = logits + (int64_t)row * ld;
   if (ctl) {
     a.seed = ctl[0];
     a.offset0 = ctl[1];
@@ -230,156 +405,11 @@ __global__ __launch_bounds__(1024) void sample_tail_k(const T* __restrict__ logi
   const bool tail = history != nullptr;
   const int64_t step = tail ? *step_idx : 0;
   const bool stopped = tail && a.stop_id >= 0 && tokens[row] == a.stop_id;
-  float bv = -INFINITY;
-  int bi = 0x7fffffff;
-  if (!stopped) {
-    if (a.top_k == 1) {
-      row_for_each<T>(lr, V, tid, [&](float x, int i) { take(bv, bi, x, i); });
-    } else {
-      const float temp = a.temperature;
-      const bool topk = a.top_k > 1, topp = !topk && a.top_p > 0.f;
-      uint32_t kstar = 0;
-      const uint64_t off = (uint64_t)(a.offset0 + step), seed = (uint64_t)a.seed;
-      const uint64_t chi = (uint64_t)row << 32;
-      auto draw = [&](float y, int i) {
-        const U4 r = philox(chi | (uint32_t)(i >> 2), off, seed);
-        const int q = i & 3;
-        const uint32_t w = q == 0 ? r.x : q == 1 ? r.y : q == 2 ? r.z : r.w;
-        take(bv, bi, y + gumbel(w), i);
-      };
-      if (!(topk || topp)) {
-        row_for_each<T>(lr, V, tid, [&](float x, int i) { draw(tempered(x, temp), i); });
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) hist[4 * tid + j] = 0;
-        if (tid == 0) ncand = 0;
-        float m = 0.f;
-        if (topp) {
-          float lm = -INFINITY;
-          row_for_each<T>(lr, V, tid, [&](float x, int) { lm = fmaxf(lm, tempered(x, temp)); });
-          m = block_max(lm, sv);
-        }
-        __syncthreads();
-        u64 carry = 0, budget = topk ? (u64)(a.top_k - 1) : 0;
-        unsigned nlist = 0;
-        bool in_list = false;  // the threshold bin's elements are in ckey / cidx
-        for (int p = 0; p < 3; ++p) {
-          const int shift = p == 0 ? 20 : p == 1 ? 10 : 0;
-          const int bits = p == 0 ? 12 : 10;
-          const uint32_t prefix = kstar;
-          auto add = [&](float y, uint32_t k) {
-            if (p == 0 || (k >> (shift + bits)) == prefix) {
-              u64 w = 1;
-              // fixed-point softmax numerator, exp(y - max) * 2^40 <= 2^40:
-              // V <= 2^22 of them sum below 2^63 (hardware exp2: the argument's
-              // rounding is < 3e-6 relative at y - max = -30, where the mass is nil)
-              if (topp) w = y == -INFINITY ? 0 : (u64)(__expf(y - m) * 0x1p40f);
-              atomicAdd(&hist[(k >> shift) & ((1u << bits) - 1u)], w);
-            }
-          };
-          if (in_list) {
-            for (unsigned c = tid; c < nlist; c += ST_NT) add(unkey(ckey[c]), ckey[c]);
-          } else {
-            row_for_each<T>(lr, V, tid, [&](float x, int) {
-              const float y = tempered(x, temp);
-              add(y, okey(y));
-            });
-          }
-          __syncthreads();
-          u64 h[4], loc = 0;
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            h[j] = hist[4 * tid + j];
-            hist[4 * tid + j] = 0;
-            loc += h[j];
-          }
-          // inclusive suffix sum over the 1024 threads (integers: exact)
-          u64 incl = loc;
-#pragma unroll
-          for (int o = 1; o < 64; o <<= 1) {
-            const u64 t = __shfl_down(incl, o, 64);
-            if (lane + o < 64) incl += t;
-          }
-          if (lane == 0) swt[wave] = incl;
-          __syncthreads();
-          u64 after = 0, total = 0;
-#pragma unroll
-          for (int w = 0; w < ST_NT / 64; ++w) {
-            const u64 v = swt[w];
-            total += v;
-            if (w > wave) after += v;
-          }
-          if (p == 0 && topp)
-            budget = a.top_p >= 1.f ? total : (u64)((double)a.top_p * (double)total);
-          // above[j]: weight strictly above bin 4 tid + j; the digit is the
-          // smallest bin with above <= budget (exactly one bin qualifies)
-          u64 above = carry + after + (incl - loc);
-#pragma unroll
-          for (int j = 3; j >= 0; --j) {
-            const u64 below = above + h[j];  // weight above bin 4 tid + j - 1
-            if (above <= budget && (below > budget || 4 * tid + j == 0)) {
-              ssel[0] = (u64)(4 * tid + j);
-              ssel[1] = above;
-            }
-            above = below;
-          }
-          __syncthreads();
-          kstar = (kstar << bits) | (uint32_t)ssel[0];
-          carry = ssel[1];
-          if (p == 0) {
-            // the first digit d of K* is known: every element of a bin above d
-            // is kept and drawn now; bin d's (key, index) go to an LDS list,
-            // from which the two lower digits and the last draws are taken
-            // (the row is read again for them only if the list overflows)
-            const uint32_t d = kstar;
-            row_for_each<T>(lr, V, tid, [&](float x, int i) {
-              const float y = tempered(x, temp);
-              const uint32_t k = okey(y);
-              if ((k >> 20) > d) {
-                draw(y, i);
-              } else if ((k >> 20) == d) {
-                const unsigned c = atomicAdd(&ncand, 1u);
-                if (c < ST_CAP) {
-                  ckey[c] = k;
-                  cidx[c] = i;
-                }
-              }
-            });
-            __syncthreads();
-            nlist = ncand;
-            in_list = nlist <= ST_CAP;
-          }
-        }
-        if (in_list) {
-          for (unsigned c = tid; c < nlist; c += ST_NT)
-            if (ckey[c] >= kstar) draw(unkey(ckey[c]), cidx[c]);
-        } else {
-          row_for_each<T>(lr, V, tid, [&](float x, int i) {
-            const float y = tempered(x, temp);
-            const uint32_t k = okey(y);
-            if ((k >> 20) == (kstar >> 20) && k >= kstar) draw(y, i);
-          });
-        }
-      }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      take(bv, bi, ov, oi);
-    }
-    __syncthreads();
-    if (lane == 0) {
-      sv[wave] = bv;
-      si[wave] = bi;
-    }
-    __syncthreads();
-  }
+  int bi = 0;
+  if (!stopped) bi = draw_row<T>(lr, V, row, tid, a, step);
   if (tid != 0) return;
   int64_t tok = a.stop_id;
   if (!stopped) {
-#pragma unroll
-    for (int w = 1; w < ST_NT / 64; ++w) take(bv, bi, sv[w], si[w]);
     tok = bi;
     if (a.vocab_limit > 0 && tok >= a.vocab_limit) tok = a.vocab_limit - 1;
   }
@@ -402,7 +432,82 @@ __global__ __launch_bounds__(1024) void sample_tail_k(const T* __restrict__ logi
   }
 }
 
+// ---------------------------------------------------------------- ragged tails
+// ragged_tail_k (inference/continuous.py): the tail of a decode step whose rows
+// are independent sequences.  Every row has its own history index, cache slot,
+// key count, position, limit and an `active` flag (RaggedTail); shared are the
+// replay count *tick and ctl / fctl of the sampling tail.  SAMPLE: draw_row
+// with the noise at Philox offset offset0 + *tick (a refilled row starts at
+// history index 0 again and must not replay its predecessor's noise), else
+// argmax_row.  A row with active == 0 reads no logits and writes nothing.  An
+// active row stores its token (tokens, history[row, hist_idx]) and advances
+// hist_idx; if the token is stop_id (stop_id >= 0) or hist_idx reached its
+// limit the row parks itself: active = 0, and pos / slot / kv_len stay, so a
+// parked row keeps rewriting a cache slot it owns (never the one at the
+// capacity); otherwise the three advance by one.  The arrival counter's high
+// bits count the rows still active; the last workgroup advances *tick, writes
+// that count to ctl[5] and re-arms the counter.
+template <typename T, bool SAMPLE>
+__global__ __launch_bounds__(1024) void ragged_tail_k(const T* __restrict__ logits, int64_t ld, int V,
+                                                     int64_t* tokens, int64_t* history,
+                                                     int64_t hist_ld, int64_t hist_cols,
+                                                     RaggedTail st, unsigned* counter, int64_t* ctl,
+                                                     const float* fctl) {
+  const int row = blockIdx.x, tid = threadIdx.x;
+  const bool act = st.active[row] != 0;
+  const int64_t stop_id = ctl[4];
+  int bi = 0;
+  if (act) {
+    const T* lr = logits + (int64_t)row * ld;
+    if constexpr (SAMPLE) {
+      const SampleArgs a{ctl[0], ctl[1], ctl[2], ctl[3], stop_id, fctl[0], fctl[1]};
+      bi = draw_row<T>(lr, V, row, tid, a, *st.tick);
+    } else {
+      bi = argmax_row<T>(lr, V, tid);
+    }
+  }
+  if (tid != 0) return;
+  unsigned still = 0u;
+  if (act) {
+    int64_t tok = bi;
+    if (SAMPLE && ctl[3] > 0 && tok >= ctl[3]) tok = ctl[3] - 1;
+    const int64_t hi = st.hist_idx[row];
+    tokens[row] = tok;
+    if (hi >= 0 && hi < hist_cols) history[(int64_t)row * hist_ld + hi] = tok;
+    st.hist_idx[row] = hi + 1;
+    if ((stop_id >= 0 && tok == stop_id) || hi + 1 >= st.limit[row]) {
+      st.active[row] = 0;
+    } else {
+      st.pos[row] += 1;
+      st.slot[row] += 1;
+      st.kv_len[row] += 1;
+      still = 1u;
+    }
+  }
+  // every workgroup has read *tick (its draw used it) before it arrives
+  const unsigned prev = __hip_atomic_fetch_add(counter, 1u + (still << 16), __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_AGENT);
+  if ((prev & 0xffffu) == gridDim.x - 1) {
+    *st.tick += 1;
+    ctl[5] = (int64_t)((prev >> 16) + still);
+    __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 }  // namespace
+
+void ragged_tail(const void* logits, int64_t ld, int V, int b, int dt, bool sample, int64_t* tokens,
+                 int64_t* history, int64_t hist_ld, int64_t hist_cols, const RaggedTail& st,
+                 unsigned* counter, int64_t* ctl, const float* fctl, hipStream_t s) {
+  EMA_DISPATCH_FLOAT(dt, T, {
+    if (sample)
+      hipLaunchKernelGGL((ragged_tail_k<T, true>), dim3((unsigned)b), dim3(1024), 0, s, (const T*)logits,
+                         ld, V, tokens, history, hist_ld, hist_cols, st, counter, ctl, fctl);
+    else
+      hipLaunchKernelGGL((ragged_tail_k<T, false>), dim3((unsigned)b), dim3(1024), 0, s, (const T*)logits,
+                         ld, V, tokens, history, hist_ld, hist_cols, st, counter, ctl, fctl);
+  });
+}
 
 void greedy_tail(const void* logits, int64_t ld, int V, int b, int dt, int64_t* tokens,
                  int64_t* history, int64_t hist_ld, int64_t* step_idx, int64_t* pos, int64_t* slot,

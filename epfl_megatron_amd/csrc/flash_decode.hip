@@ -26,7 +26,10 @@
 //
 // With a device-side key count (DecodeParams::kv_len) the launch is
 // independent of the step, so the whole decode step can be captured once in
-// a hipGraph and replayed (inference/hip_graph.py).  A sliding window
+// a hipGraph and replayed (inference/hip_graph.py).  The count is one value
+// for the batch or one per sequence (DecodeParams::kv_len_sb: ragged decode,
+// inference/continuous.py; the grid stays sized for the capacity and a row's
+// chunks past its own length leave empty partials).  A sliding window
 // (DecodeParams::window) keeps the last `window` of the valid keys, bounded on
 // the device the same way.
 //
@@ -107,7 +110,8 @@ __global__ __launch_bounds__(256) void decode_attn_k(const DecodeParams p) {
   const int g = blockIdx.y / nhs, hs = blockIdx.y % nhs, b = blockIdx.z;
   const int h0 = hs * RH, nh = min(RH, r - h0);  // heads g*r + h0 .. + nh - 1
   const int k0 = chunk * DCH;
-  const int sk = p.kv_len ? min(*p.kv_len, p.sk) : p.sk;
+  // (b is uniform: a scalar load in the per-row form too)
+  const int sk = p.kv_len ? min(p.kv_len[(int64_t)b * p.kv_len_sb], p.sk) : p.sk;
   // sliding window: only keys [klo, sk) count; a chunk wholly below klo leaves
   // the empty partial of a chunk past the length, the straddling one masks
   const int klo = p.window > 0 ? max(sk - p.window, 0) : 0;
@@ -482,7 +486,7 @@ __global__ __launch_bounds__(256) void kv_store_fp8_k(const KvStoreParams p) {
                  (int64_t)bb * (isv ? p.v_sb : p.k_sb) + (int64_t)g * (isv ? p.v_sg : p.k_sg) + 8 * c;
   const typename fa::MT<T>::x8 x = fa::ld8(src);
   const float inv = 1.0f / p.scales[(isv ? p.nkv : 0) + g];
-  const int64_t slot = p.slot_ptr ? *p.slot_ptr : p.slot;
+  const int64_t slot = p.slot_ptr ? p.slot_ptr[bb * p.slot_sb] : p.slot;
   float f[8];
 #pragma unroll
   for (int e = 0; e < 8; ++e) f[e] = fminf(fmaxf((float)x[e] * inv, -448.f), 448.f);

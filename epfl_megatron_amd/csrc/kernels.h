@@ -212,6 +212,10 @@ struct DecodeParams {
   // sized for sk (the cache capacity) and chunks past the length exit early,
   // so one launch serves every step of a captured hipGraph decode loop.
   const int* kv_len;
+  // 0: *kv_len holds for the whole batch; 1: sequence b has kv_len[b] valid
+  // keys (ragged decode: chunks past a row's own length leave empty partials,
+  // a row of length 0 gives exact zeros)
+  int kv_len_sb;
   // zeroed uint32 [flash_decode_counters()]: arrivals per (batch, head slice)
   // when a sequence is split over several workgroups; the last one to arrive
   // combines the chunk partials and re-arms its counter
@@ -231,7 +235,8 @@ int flash_decode_kpw(int b, int sk, int nq, int nkv);
 // Quantising KV-cache store: k / v [sq, b, nkv, hd] of dt (element strides
 // *_ss / *_sb / *_sg, hd contiguous) -> e4m3fn rows slot .. slot + sq - 1 of
 // the caches [L, B, nkv, hd] (byte strides c_ss / c_sb, packed heads), slot
-// from *slot_ptr when given.  byte = e4m3_rne(clamp(x / scale[head], +-448)),
+// from *slot_ptr when given (slot_sb == 1, sq == 1: sequence b's row goes to
+// slot_ptr[b]).  byte = e4m3_rne(clamp(x / scale[head], +-448)),
 // scales fp32 [2, nkv] (row 0: K, row 1: V).  One launch covers K and V.
 struct KvStoreParams {
   const void* k;
@@ -242,6 +247,7 @@ struct KvStoreParams {
   int sq, b, nkv, hd;
   int64_t slot;
   const int64_t* slot_ptr;
+  int64_t slot_sb;
   const float* scales;
 };
 void kv_store_fp8(const KvStoreParams& p, int dt, hipStream_t s);
@@ -268,6 +274,22 @@ void sample_tail(const void* logits, int64_t ld, int V, int b, int dt, int64_t* 
                  int64_t* history, int64_t hist_ld, int64_t hist_cols, int64_t* step_idx, int64_t* pos,
                  int64_t* slot, int* kv_len, unsigned* counter, int64_t* ctl, const float* fctl, SampleArgs a,
                  hipStream_t s);
+// Ragged forms of both tails (continuous batching): per-row state, all [b]
+// except tick [1]; semantics at ragged_tail_k in decode_tail.hip.  ctl / fctl
+// as above (the greedy form reads only stop_id, ctl[4]); ctl[5] receives the
+// number of rows still active.
+struct RaggedTail {
+  int64_t* hist_idx;
+  int64_t* slot;
+  int* kv_len;
+  int64_t* pos;
+  int* active;
+  const int64_t* limit;
+  int64_t* tick;
+};
+void ragged_tail(const void* logits, int64_t ld, int V, int b, int dt, bool sample, int64_t* tokens,
+                 int64_t* history, int64_t hist_ld, int64_t hist_cols, const RaggedTail& st,
+                 unsigned* counter, int64_t* ctl, const float* fctl, hipStream_t s);
 int flash_decode_splits(int sk, int kpw);
 int flash_decode_counters(int b, int nq, int nkv);
 void flash_decode(const DecodeParams& p, int dt, hipStream_t s);
@@ -372,6 +394,8 @@ struct SkinnyArgs {
   const int64_t* slot_ptr;  // device slot index (graph decode) or nullptr: `slot`
   int64_t slot;
   int packed;           // 1: w is in the decode-packed layout (skinny_pack, K % 256 == 0)
+  int slot_sb;          // 0: *slot_ptr for every row; 1: row m writes at slot_ptr[m] (ragged
+                        // decode).  (an int in the padding after `packed`: same kernarg size)
   // FP8 weight-only decode: non-null = w holds OCP e4m3fn bytes in the packed
   // FP8 layout (ops/fp8_weights.py) and w_scale[row] (fp32, original W row
   // order: [N], GLU [2N] up rows then gate rows) multiplies the fp32 sums

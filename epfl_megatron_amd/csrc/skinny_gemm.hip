@@ -31,7 +31,8 @@
 //     Meta-convention rotary embedding at the token's absolute position
 //     (pairs 2i, 2i+1: inside one lane's 4 features), q goes to Y [M, nq*hd],
 //     k and v straight into the KV cache slot (device-resident slot index, so
-//     the step is graph-capturable).
+//     the step is graph-capturable; one index for the batch, or one per row
+//     with SkinnyArgs::slot_sb: ragged decode, inference/continuous.py).
 // Shapes: M <= 32 (17-32 rows: two row blocks per W fragment in the
 // per-block kernel), N % 16 == 0, K % 128 == 0 (checked by the host).
 //
@@ -284,6 +285,42 @@ __device__ __forceinline__ void epilogue(const SkinnyArgs& p, int blk, const f4&
     if (h < p.r) {
       dst = y + (int64_t)m * p.ldy + (int64_t)(g * p.r + h) * hd + d;
     } else {
+      if (p.slot_sb) {
+        // per-row slots (ragged decode; a wave-uniform branch): one pass per
+        // row of the block, the row's slot a scalar load as in the scalar
+        // form, the lanes of that row store; four slots fetched per round
+        // (indices clamped to the block's last row).  No per-lane slot: the
+        // persistent forms have no VGPRs to spare beside the k-loop's
+        // (profiles/r15a_ragged_isa.txt).  Rows m >= M have returned above.
+        const int rows = min(16, M - moff);
+#pragma unroll 1
+        for (int i0 = 0; i0 < rows; i0 += 4) {
+          int64_t sl4[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) sl4[u] = p.slot_ptr[moff + min(i0 + u, rows - 1)];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            if (m != moff + i0 + u) continue;
+            const int64_t sl = sl4[u];
+            if (p.kv_scale) {
+              const float inv = use_pre ? pre.kvr : kv_rscale(p, n);
+              float f[4];
+#pragma unroll
+              for (int e = 0; e < 4; ++e) f[e] = fminf(fmaxf((float)o[e] * inv, -448.f), 448.f);
+              int w = 0;
+              w = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], w, false);
+              w = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w, true);
+              uint8_t* c8 = (uint8_t*)(h == p.r ? p.kcache : p.vcache);
+              *reinterpret_cast<int*>(c8 + sl * p.c_ss + (int64_t)m * p.c_sb + (int64_t)g * hd + d) = w;
+            } else {
+              T* cache = (T*)(h == p.r ? p.kcache : p.vcache);
+              *reinterpret_cast<typename fa::MT<T>::x4*>(cache + sl * p.c_ss + (int64_t)m * p.c_sb +
+                                                         (int64_t)g * hd + d) = o;
+            }
+          }
+        }
+        return;
+      }
       const int64_t slot = use_pre ? pre.slot : p.slot_ptr ? *p.slot_ptr : p.slot;
       if (p.kv_scale) {
         // e4m3 cache: the lane's 4 consecutive dims of one token and head, as

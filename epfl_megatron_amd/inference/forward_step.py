@@ -27,7 +27,8 @@ class InferenceParams:
         self.batch_size_offset = 0
         self.key_value_memory_dict = {}
         # hipGraph decode (inference/hip_graph.py): the cache slot of the new
-        # token (int64 [1]) and the valid key count (int32 [1]) on the device
+        # token (int64 [1]) and the valid key count (int32 [1]) on the device;
+        # [batch] elements each: one per row (inference/continuous.py)
         self.device_offset = None
         self.device_kv_len = None
         # FP8 KV cache (--inference_fp8_kv_cache): per layer an fp32 device

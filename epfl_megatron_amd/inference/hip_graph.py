@@ -10,7 +10,10 @@ eager, 5.6 vs 7.0-8.2 at batch 32 (``profiles/r2f_serve_graph.txt``).
 
 What makes the step capturable: nothing in it depends on the step on the host.
   * the token's cache slot and the number of valid keys are device tensors
-    (``InferenceParams.device_offset`` / ``device_kv_len``): the K/V write is
+    (``InferenceParams.device_offset`` / ``device_kv_len``; one element for a
+    batch in lockstep, as every class of this file keeps them, or one per row:
+    the ragged decoders and the continuous batcher of ``continuous.py``, which
+    the kernels tell from the element count): the K/V write is
     an ``index_copy_`` and the decode attention reads the key count on the
     device (``csrc/flash_decode.hip``, grid sized for the whole cache, chunks
     past the length exit early);

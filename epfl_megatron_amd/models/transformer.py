@@ -484,8 +484,14 @@ class ParallelAttention(MegatronModule):
                 raise NotImplementedError("hipGraph decode needs the native decode attention "
                                           "kernel (GPU, bf16/fp16, head_dim 64 or 128)")
             kc, vc = kmem[:, b0:b0 + b], vmem[:, b0:b0 + b]
-            kc.index_copy_(0, ip.device_offset, k)
-            vc.index_copy_(0, ip.device_offset, v)
+            if b > 1 and ip.device_offset.numel() == b:
+                # one slot per sequence (ragged decode, inference/continuous.py)
+                rows = torch.arange(b, device=k.device)
+                kc[ip.device_offset, rows] = k[0]
+                vc[ip.device_offset, rows] = v[0]
+            else:
+                kc.index_copy_(0, ip.device_offset, k)
+                vc.index_copy_(0, ip.device_offset, v)
             o = flash_decode_cached(q.transpose(0, 1), kc.transpose(0, 1), vc.transpose(0, 1),
                                     ip.device_kv_len, window=self._window(kc.shape[0]))
             return o.transpose(0, 1).reshape(sq, b, -1)

@@ -175,9 +175,21 @@ def flash_decode_cached(q, k, v, kv_len, softmax_scale=None, window=0, kv_scale=
     nkv, d]`` of which the first ``kv_len`` (device int32) keys are valid
     (with ``window``: the last ``window`` of those).  ``kv_len`` None: all
     ``smax`` keys are valid.  ``kv_scale``: fp32 ``[2, nkv]`` when k / v are an
-    FP8 cache (uint8 e4m3fn bytes, ``ops/fp8_kv.py``)."""
+    FP8 cache (uint8 e4m3fn bytes, ``ops/fp8_kv.py``).  A ``kv_len`` of ``b >
+    1`` elements holds one length per sequence (ragged decode): row ``i`` sees
+    the keys ``[max(0, n_i - window), n_i)``, none (zeros) at ``n_i == 0``."""
     _check_window(window, True)
     if not use_native(q):
+        if kv_len is not None and q.shape[0] > 1 and kv_len.numel() == q.shape[0]:
+            rows = []
+            for i, n in enumerate(kv_len.reshape(-1).tolist()):
+                if min(n, k.shape[1]) <= 0:
+                    rows.append(torch.zeros_like(q[i:i + 1]))
+                else:
+                    rows.append(flash_decode_cached(q[i:i + 1], k[i:i + 1], v[i:i + 1],
+                                                    kv_len.reshape(-1)[i:i + 1], softmax_scale,
+                                                    window, kv_scale))
+            return torch.cat(rows, 0)
         n = int(kv_len.reshape(-1)[0]) if kv_len is not None else k.shape[1]
         lo = max(n - window, 0) if window else 0
         k, v = k[:, lo:n], v[:, lo:n]

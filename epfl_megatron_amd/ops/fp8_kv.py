@@ -69,14 +69,19 @@ def store_native_ok(k):
 def store(k, v, kcache, vcache, scales, slot=0, slot_t=None):
     """Quantise ``k / v [sq, b, nkv, hd]`` into rows ``slot .. slot + sq - 1`` of
     the caches ``[L, >= b, nkv, hd]`` (uint8 views at the batch offset);
-    ``slot_t``: the slot as an int64 device scalar (hipGraph decode).  One HIP
-    launch on the GPU, the torch quantiser elsewhere."""
+    ``slot_t``: the slot as an int64 device scalar (hipGraph decode), or with
+    ``sq == 1`` and ``b > 1`` elements one slot per sequence (ragged decode).
+    One HIP launch on the GPU, the torch quantiser elsewhere."""
     sq, b = k.shape[:2]
     if store_native_ok(k) and store_native_ok(v):
         ext().kv_store_fp8(k, v, kcache, vcache, scales, slot_t, int(slot))
         return
     qk, qv = quantize(k, scales[0]), quantize(v, scales[1])
-    if slot_t is not None:
+    if slot_t is not None and sq == 1 and b > 1 and slot_t.numel() == b:
+        rows = torch.arange(b, device=qk.device)
+        kcache[slot_t, rows] = qk[0]
+        vcache[slot_t, rows] = qv[0]
+    elif slot_t is not None:
         kcache[:, :b].index_copy_(0, slot_t, qk)
         vcache[:, :b].index_copy_(0, slot_t, qv)
     else:

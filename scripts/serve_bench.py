@@ -12,8 +12,23 @@ GraphedSamplingDecoder under --graph (the draw is inside the graph), else by
 one fused launch per step (ops/sampling.py sample_fused; --eager_sample runs
 inference/sampling.py's sort / softmax / multinomial chain for comparison).
 
+--continuous: a fixed, seeded list of requests (prompt and generation lengths
+drawn once from --prompt_range / --gen_range) served by ContinuousBatcher
+(inference/continuous.py: ragged decode, finished rows refilled between replays
+of one captured graph) at each batch size, and, where the lockstep decoders can
+serve them at all (uniform prompts), the same requests in groups of B through
+GraphedGreedyDecoder / GraphedSamplingDecoder, each group running to its longest
+member.  Reports useful tokens/s (tokens a request asked for, prefill time
+included) for both; with a prompt-length range the baseline is "not possible".
+
+--ragged_cost: what per-row state costs a uniform batch: RaggedGreedyDecoder
+against GraphedGreedyDecoder from the same prefilled cache, --reps repetitions
+each, alternating; the spread of the lockstep decoder's repetitions is the margin.
+
 Usage: python scripts/serve_bench.py [--batches 1,8,32] [--graph]
        [--top_k K | --top_p P] [--temperature T]
+       [--continuous [--requests N] [--prompt_range LO,HI] [--gen_range LO,HI]
+        [--poll_every 1,4,16]] [--ragged_cost [--reps 3]]
 """
 import argparse
 import json
@@ -44,6 +59,19 @@ def main():
                     help="MXFP4 weight-only decode (--inference_mxfp4_weights; ops/mxfp4_weights.py)")
     ap.add_argument("--fp8_kv_cache", action="store_true",
                     help="FP8 KV cache (--inference_fp8_kv_cache; ops/fp8_kv.py)")
+    ap.add_argument("--continuous", action="store_true",
+                    help="serve a seeded request list through ContinuousBatcher (and the lockstep "
+                         "baseline where it exists)")
+    ap.add_argument("--requests", type=int, default=0, help="--continuous: requests (0: 4 x batch)")
+    ap.add_argument("--prompt_range", default="128,128", help="--continuous: prompt lengths LO,HI")
+    ap.add_argument("--gen_range", default="16,256", help="--continuous: generation lengths LO,HI")
+    ap.add_argument("--poll_every", default="4", help="--continuous: values to run, comma separated")
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--ragged_cost", action="store_true",
+                    help="RaggedGreedyDecoder against GraphedGreedyDecoder on a uniform batch")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--only", choices=["lockstep", "ragged"], default=None,
+                    help="--ragged_cost: run one of the two decoders (a per-kernel profile of each)")
     a = ap.parse_args()
     sampling = a.top_k > 0 or a.top_p > 0.0 or a.temperature != 1.0
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=os.environ.get("MASTER_PORT", "29561"),
@@ -84,6 +112,10 @@ def main():
     initialize_megatron(finetune.extra_args, {"tokenizer_type": "NullTokenizer"}, args_list=argv)
     model = get_model(finetune.model_provider, ModelType.encoder_or_decoder, wrap_with_ddp=False)
     m = model[0].eval()
+    if a.continuous:
+        return continuous(a, m, sampling, skw)
+    if a.ragged_cost:
+        return ragged_cost(a, m)
     res = []
     for B in [int(x) for x in a.batches.split(",")]:
         total = a.prompt + a.gen
@@ -125,6 +157,135 @@ def main():
              "prompt": a.prompt, "gen": a.gen, "prefill_ms": round(1e3 * (t1 - t0), 2),
              "decode_ms_per_step": round(1e3 * (t2 - t1) / steps, 3),
              "decode_tokens_per_s": round(B * steps / (t2 - t1), 1)}
+        print(json.dumps(r), flush=True)
+        res.append(r)
+    return res
+
+
+def _timed(fn):
+    import torch
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return out, time.perf_counter() - t0
+
+
+def continuous(a, m, sampling, skw):
+    """--continuous: useful tokens/s of ContinuousBatcher and of the lockstep
+    decoders on one seeded request list per batch size."""
+    import torch
+    from epfl_megatron_amd.inference import ContinuousBatcher, RaggedSamplingDecoder
+    from epfl_megatron_amd.inference.forward_step import InferenceParams
+    from epfl_megatron_amd.inference.hip_graph import GraphedGreedyDecoder, GraphedSamplingDecoder
+    from epfl_megatron_amd.ops.sampling import sample_fused
+    (plo, phi), (glo, ghi) = ([int(x) for x in r.split(",")] for r in (a.prompt_range, a.gen_range))
+    cap = phi + ghi
+    res = []
+    for B in [int(x) for x in a.batches.split(",")]:
+        n = a.requests or 4 * B
+        g = torch.Generator().manual_seed(a.seed)
+        plens = torch.randint(plo, phi + 1, (n,), generator=g).tolist()
+        gens = torch.randint(glo, ghi + 1, (n,), generator=g).tolist()
+        prompts = [torch.randint(0, 32000, (p,), generator=g) for p in plens]
+        useful = sum(gens)
+        base = {"mode": "continuous", "batch": B, "requests": n, "prompt_range": [plo, phi],
+                "gen_range": [glo, ghi], "useful_tokens": useful,
+                "sampling": dict(skw) if sampling else "greedy"}
+        for poll in [int(x) for x in a.poll_every.split(",")]:
+            ip = InferenceParams(B, cap)
+            dec = None
+            if sampling:
+                dec = RaggedSamplingDecoder(m, ip, B, ghi, vocab_size=32000)
+                dec.configure(**skw)
+            cb = ContinuousBatcher(m, ip, B, cap, poll_every=poll, max_new_tokens=ghi, decoder=dec)
+            for p in prompts[:B]:  # warm-up: the capture, the allocator, the prefill kernels
+                cb.submit(p, 4)
+            cb.run()
+            warm = cb.replays
+            for p, gn in zip(prompts, gens):
+                cb.submit(p, gn)
+            out, dt = _timed(cb.run)
+            assert [len(o) for o in out[-n:]] == gens and cb.dec.captures == 1
+            r = dict(base, poll_every=poll, replays=cb.replays - warm, seconds=round(dt, 3),
+                     continuous_tokens_per_s=round(useful / dt, 1))
+            if plo != phi:
+                r["static_tokens_per_s"] = "not possible"
+            res.append(r)
+        if plo == phi:  # the lockstep baseline: groups of B, each to its longest member
+            ip = InferenceParams(B, cap)
+            pos = torch.arange(cap, device="cuda")[None].expand(B, -1)
+            dec = GraphedSamplingDecoder(m, ip, B, ghi, vocab_size=32000) if sampling else \
+                GraphedGreedyDecoder(m, ip, B, ghi)
+
+            def static(groups):
+                steps = 0
+                with torch.no_grad():
+                    for i in range(0, groups * B, B):
+                        grp = [prompts[min(j, n - 1)] for j in range(i, i + B)]  # last group: padded
+                        ip.sequence_len_offset = 0
+                        lg = m(torch.stack(grp).cuda(), pos[:, :plo], None, inference_params=ip)[:, -1]
+                        nxt = sample_fused(lg, vocab_size=32000, **skw) if sampling else lg.argmax(-1)
+                        ip.sequence_len_offset = plo
+                        dec.start(nxt.view(B, 1), plo, **(skw if sampling else {}))
+                        for _ in range(max(gens[i:i + B]) - 1):
+                            dec.step()
+                        steps += max(gens[i:i + B]) - 1
+                return steps
+            static(1)  # warm-up and capture
+            steps, dt = _timed(lambda: static(-(-n // B)))
+            for r in res[-len(a.poll_every.split(",")):]:
+                r.update(static_tokens_per_s=round(useful / dt, 1), static_seconds=round(dt, 3),
+                         static_replays=steps)
+        for r in res[-len(a.poll_every.split(",")):]:
+            print(json.dumps(r), flush=True)
+    return res
+
+
+def ragged_cost(a, m):
+    """--ragged_cost: decode ms/step of the ragged and the lockstep greedy
+    decoder on a uniform batch, alternating repetitions."""
+    import torch
+    from epfl_megatron_amd.inference import RaggedGreedyDecoder
+    from epfl_megatron_amd.inference.forward_step import InferenceParams
+    from epfl_megatron_amd.inference.hip_graph import GraphedGreedyDecoder
+    res = []
+    steps = a.gen - 1
+    for B in [int(x) for x in a.batches.split(",")]:
+        total = a.prompt + a.gen
+        torch.manual_seed(0)
+        prompt = torch.randint(0, 32000, (B, a.prompt), device="cuda")
+        pos = torch.arange(total, device="cuda")[None].expand(B, -1)
+        decs, ms = {}, {"lockstep": [], "ragged": []}
+        with torch.no_grad():
+            for name in ([a.only] if a.only else ["lockstep", "ragged"]):
+                ip = InferenceParams(B, total)
+                nxt = m(prompt, pos[:, :a.prompt], None, inference_params=ip)[:, -1].argmax(-1)
+                ip.sequence_len_offset = a.prompt
+                dec = GraphedGreedyDecoder(m, ip, B, a.gen) if name == "lockstep" else \
+                    RaggedGreedyDecoder(m, ip, B, a.gen)
+                decs[name] = (dec, nxt)
+            for rep in range(a.reps + 1):  # rep 0: capture and warm-up
+                for name, (dec, nxt) in decs.items():
+                    if name == "lockstep":
+                        dec.start(nxt.view(B, 1), a.prompt)
+                    else:
+                        for row in range(B):
+                            dec.prime(row, int(nxt[row]), a.prompt, a.gen)
+
+                    def run():
+                        for _ in range(steps):
+                            dec.step()
+                    _, dt = _timed(run)
+                    if rep:
+                        ms[name].append(round(1e3 * dt / steps, 4))
+        r = {"mode": "ragged_cost", "batch": B, "prompt": a.prompt, "gen": a.gen,
+             "lockstep_ms_per_step": ms["lockstep"], "ragged_ms_per_step": ms["ragged"]}
+        if not a.only:
+            r.update(lockstep_spread_ms=round(max(ms["lockstep"]) - min(ms["lockstep"]), 4),
+                     ragged_minus_lockstep_ms=round((sum(ms["ragged"]) - sum(ms["lockstep"])) / a.reps, 4),
+                     same_tokens=torch.equal(decs["lockstep"][0].history[:, :steps],
+                                             decs["ragged"][0].history[:, :steps]))
         print(json.dumps(r), flush=True)
         res.append(r)
     return res
