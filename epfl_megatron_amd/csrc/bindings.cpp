@@ -952,9 +952,24 @@ void flash_decode(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
                   int64_t b, int64_t sk, int64_t nq, int64_t nkv, int64_t hd,
                   std::vector<int64_t> qs, std::vector<int64_t> ks, std::vector<int64_t> vs,
                   std::vector<int64_t> os, double scale, const c10::optional<at::Tensor>& kv_len,
-                  int64_t kpw, int64_t window, const c10::optional<at::Tensor>& kv_scale) {
+                  int64_t kpw, int64_t window, const c10::optional<at::Tensor>& kv_scale,
+                  const c10::optional<at::Tensor>& page_table) {
   check_gpu(q, "q");
   TORCH_CHECK(window >= 0, "sliding window must be >= 0 (0: none)");
+  // paged cache: k / v are the pool [n_pages * KV_PAGE, nkv, hd] rows (strides
+  // ks / vs = (unused, row, group)), page_table int32 [>= b, pt_ld]
+  int64_t pt_ld = 0, n_pages = 0;
+  if (page_table) {
+    TORCH_CHECK(page_table->scalar_type() == at::kInt, "page_table must be an int32 tensor");
+    TORCH_CHECK(page_table->is_cuda() && page_table->device() == q.device(),
+                "page_table must be on q's device");
+    TORCH_CHECK(page_table->dim() == 2 && page_table->is_contiguous() && page_table->size(0) >= b &&
+                page_table->size(1) >= 1, "page_table must be 2-D contiguous [>= b, pages_per_row]");
+    pt_ld = page_table->size(1);
+    TORCH_CHECK(sk <= pt_ld * ema::KV_PAGE, "sk exceeds the page_table's ", pt_ld, " pages of ",
+                ema::KV_PAGE, " keys per row");
+    TORCH_CHECK(kv_len.has_value(), "a page_table needs kv_len (the keys each row's pages hold)");
+  }
   // FP8 KV cache: k / v uint8 (e4m3fn bytes) with fp32 scales [2, nkv]
   const bool kv8 = k.scalar_type() == at::kByte || v.scalar_type() == at::kByte;
   TORCH_CHECK(k.scalar_type() == v.scalar_type(), "k / v cache dtypes differ");
@@ -983,9 +998,20 @@ void flash_decode(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
   auto span = [](int64_t b, int64_t s, int64_t n, int64_t sb, int64_t ss, int64_t sn, int64_t hd) {
     return (b - 1) * sb + (s - 1) * ss + (n - 1) * sn + hd;
   };
-  TORCH_CHECK(k.storage_offset() + span(b, sk, nkv, ks[0], ks[1], ks[2], hd) <=
+  int64_t span_b = b, span_s = sk;
+  if (page_table) {
+    // the pool's rows: whole pages only, and every page the clamp can select
+    TORCH_CHECK(k.dim() == 4 && v.dim() == 4 && k.size(0) == 1 && v.size(0) == 1 &&
+                k.size(1) == v.size(1), "paged k / v must be pool views [1, rows, nkv, hd]");
+    n_pages = k.size(1) / ema::KV_PAGE;
+    TORCH_CHECK(n_pages >= 1 && k.size(1) == n_pages * ema::KV_PAGE && k.size(1) < (1ll << 31),
+                "the k / v pool must hold n_pages * ", ema::KV_PAGE, " rows");
+    span_b = 1;
+    span_s = n_pages * ema::KV_PAGE;
+  }
+  TORCH_CHECK(k.storage_offset() + span(span_b, span_s, nkv, ks[0], ks[1], ks[2], hd) <=
               (int64_t)(k.storage().nbytes() / k.element_size()), "k strides exceed storage");
-  TORCH_CHECK(v.storage_offset() + span(b, sk, nkv, vs[0], vs[1], vs[2], hd) <=
+  TORCH_CHECK(v.storage_offset() + span(span_b, span_s, nkv, vs[0], vs[1], vs[2], hd) <=
               (int64_t)(v.storage().nbytes() / v.element_size()), "v strides exceed storage");
   ema::DecodeParams p{};
   p.q = q.data_ptr(); p.k = k.data_ptr(); p.v = v.data_ptr(); p.o = out.data_ptr();
@@ -998,6 +1024,11 @@ void flash_decode(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
   p.kv_len = kv_len ? kv_len->data_ptr<int>() : nullptr;
   // one length per sequence (ragged decode) when there is one element per row
   p.kv_len_sb = (kv_len && b > 1 && kv_len->numel() == b && kv_len->is_contiguous()) ? 1 : 0;
+  if (page_table) {
+    p.page_table = page_table->data_ptr<int>();
+    p.pt_ld = (int)pt_ld;
+    p.n_pages = (int)n_pages;
+  }
   if (kv8) {
     p.kv_fp8 = 1;
     p.k_scale = kv_scale_ptr(*kv_scale, nkv, q);
@@ -1108,7 +1139,8 @@ void sample_tail(const at::Tensor& logits, at::Tensor tokens, at::Tensor history
 void ragged_tail(const at::Tensor& logits, at::Tensor tokens, at::Tensor history,
                  at::Tensor hist_idx, at::Tensor pos, at::Tensor slot, at::Tensor kv_len,
                  at::Tensor active, at::Tensor limit, at::Tensor tick, at::Tensor counter,
-                 at::Tensor ctl, at::Tensor fctl, bool sample) {
+                 at::Tensor ctl, at::Tensor fctl, bool sample,
+                 const c10::optional<at::Tensor>& page_table, int64_t n_pages) {
   const int dt = check_sample_logits(logits, "ragged_tail");
   const int64_t b = logits.size(0), V = logits.size(1);
   for (const at::Tensor* t : {&tokens, &hist_idx, &pos, &slot, &limit})
@@ -1128,7 +1160,19 @@ void ragged_tail(const at::Tensor& logits, at::Tensor tokens, at::Tensor history
               "ragged_tail: ctl int64 [6], fctl float32 [2]");
   ema::RaggedTail st{hist_idx.data_ptr<int64_t>(), slot.data_ptr<int64_t>(), kv_len.data_ptr<int>(),
                      pos.data_ptr<int64_t>(), active.data_ptr<int>(), limit.data_ptr<int64_t>(),
-                     tick.data_ptr<int64_t>()};
+                     tick.data_ptr<int64_t>(), nullptr, 0, 0};
+  if (page_table) {
+    // paged cache: int32 [b, pages_per_row]; n_pages: the pages of the pool
+    TORCH_CHECK(page_table->is_cuda() && page_table->device() == logits.device() &&
+                    page_table->scalar_type() == at::kInt && page_table->dim() == 2 &&
+                    page_table->is_contiguous() && page_table->size(0) >= b &&
+                    page_table->size(1) >= 1 && n_pages >= 1 &&
+                    n_pages * ema::KV_PAGE < (1ll << 31),
+                "ragged_tail: page_table int32 [b, pages_per_row] on the device, n_pages >= 1");
+    st.page_table = page_table->data_ptr<int>();
+    st.pt_ld = (int)page_table->size(1);
+    st.n_pages = (int)n_pages;
+  }
   ema::ragged_tail(logits.data_ptr(), logits.stride(0), (int)V, (int)b, dt, sample,
                    tokens.data_ptr<int64_t>(), history.data_ptr<int64_t>(), history.stride(0),
                    history.size(1), st, reinterpret_cast<unsigned*>(counter.data_ptr<int>()),
@@ -1529,7 +1573,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ragged_tail", &ragged_tail, py::arg("logits"), py::arg("tokens"), py::arg("history"),
         py::arg("hist_idx"), py::arg("pos"), py::arg("slot"), py::arg("kv_len"), py::arg("active"),
         py::arg("limit"), py::arg("tick"), py::arg("counter"), py::arg("ctl"), py::arg("fctl"),
-        py::arg("sample") = false);
+        py::arg("sample") = false, py::arg("page_table") = py::none(), py::arg("n_pages") = 0);
+  m.attr("KV_PAGE") = (int)ema::KV_PAGE;
   m.def("sample_rows", &sample_rows, py::arg("logits"), py::arg("tokens"), py::arg("seed"),
         py::arg("offset"), py::arg("top_k"), py::arg("top_p"), py::arg("temperature"),
         py::arg("vocab_limit"));
@@ -1552,7 +1597,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("flash_decode", &flash_decode, py::arg("q"), py::arg("k"), py::arg("v"), py::arg("out"),
         py::arg("b"), py::arg("sk"), py::arg("nq"), py::arg("nkv"), py::arg("hd"), py::arg("qs"),
         py::arg("ks"), py::arg("vs"), py::arg("os"), py::arg("scale"), py::arg("kv_len"),
-        py::arg("kpw") = 0, py::arg("window") = 0, py::arg("kv_scale") = py::none());
+        py::arg("kpw") = 0, py::arg("window") = 0, py::arg("kv_scale") = py::none(),
+        py::arg("page_table") = py::none());
   m.def("kv_store_fp8", &kv_store_fp8, py::arg("k"), py::arg("v"), py::arg("kcache"),
         py::arg("vcache"), py::arg("kv_scale"), py::arg("slot_t") = py::none(),
         py::arg("slot") = 0);

@@ -444,9 +444,11 @@ __global__ __launch_bounds__(1024) void sample_tail_k(const T* __restrict__ logi
 // hist_idx; if the token is stop_id (stop_id >= 0) or hist_idx reached its
 // limit the row parks itself: active = 0, and pos / slot / kv_len stay, so a
 // parked row keeps rewriting a cache slot it owns (never the one at the
-// capacity); otherwise the three advance by one.  The arrival counter's high
-// bits count the rows still active; the last workgroup advances *tick, writes
-// that count to ctl[5] and re-arms the counter.
+// capacity); otherwise the three advance by one (paged cache, RaggedTail::
+// page_table: the slot becomes the pool row of the new position, table[row][pos
+// / KV_PAGE] * KV_PAGE + pos % KV_PAGE, the entry clamped to the pool).  The
+// arrival counter's high bits count the rows still active; the last workgroup
+// advances *tick, writes that count to ctl[5] and re-arms the counter.
 template <typename T, bool SAMPLE>
 __global__ __launch_bounds__(1024) void ragged_tail_k(const T* __restrict__ logits, int64_t ld, int V,
                                                      int64_t* tokens, int64_t* history,
@@ -478,8 +480,15 @@ __global__ __launch_bounds__(1024) void ragged_tail_k(const T* __restrict__ logi
     if ((stop_id >= 0 && tok == stop_id) || hi + 1 >= st.limit[row]) {
       st.active[row] = 0;
     } else {
-      st.pos[row] += 1;
-      st.slot[row] += 1;
+      const int64_t np = st.pos[row] + 1;
+      st.pos[row] = np;
+      if (st.page_table) {
+        const int64_t pi = min(max(np / KV_PAGE, (int64_t)0), (int64_t)st.pt_ld - 1);
+        const int pg = st.page_table[(int64_t)row * st.pt_ld + pi];
+        st.slot[row] = (int64_t)min(max(pg, 0), st.n_pages - 1) * KV_PAGE + (np & (KV_PAGE - 1));
+      } else {
+        st.slot[row] += 1;
+      }
       st.kv_len[row] += 1;
       still = 1u;
     }

@@ -33,6 +33,14 @@
 // (DecodeParams::window) keeps the last `window` of the valid keys, bounded on
 // the device the same way.
 //
+// Paged cache (DecodeParams::page_table, inference/paged.py): k / v are a pool
+// of pages of KV_PAGE keys and row b's key i lives at pool row table[b][i /
+// KV_PAGE] * KV_PAGE + i % KV_PAGE.  A chunk (32 / 64 / 256 keys, starting at
+// a multiple of its size) never straddles a page, so the indirection is one
+// uniform table load per workgroup that moves the chunk's row base; masking,
+// scores, softmax, P.V and the combine are untouched and the result is
+// bitwise that of the same launch over the gathered contiguous cache.
+//
 // Used when it beats the FlashAttention forward on one query row (ops/attention.py
 // flash_attn_func): GQA/MQA (r >= 2: each K/V byte is read once, not r times)
 // and small grids (nq * b < 256); MHA with a full grid stays on FlashAttention
@@ -85,9 +93,13 @@ constexpr bool kFp8VWide = false;
 constexpr bool kFp8VWide = true;
 #endif
 
-template <typename T, int HD, int RH, int KPW, bool KV8>
+// PAGED: the page-table forms are instantiations of their own, so that the
+// per-row-column forms keep their registers (as a uniform runtime branch the
+// lookup cost 11 of the 96 forms 1-10 VGPRs: profiles/r16a_paged_isa.txt).
+template <typename T, int HD, int RH, int KPW, bool KV8, bool PAGED>
 __global__ __launch_bounds__(256) void decode_attn_k(const DecodeParams p) {
   constexpr int DCH = 4 * KPW;
+  static_assert(KV_PAGE % DCH == 0, "a chunk must not straddle a page");
   constexpr bool V4 = KV8 && kFp8VWide;
   constexpr int HP = V4 ? 4 : HD / 64;  // head-dim elements per lane in P.V (1 or 2; KV8: 4)
   constexpr int VR = V4 ? 256 / HD : 1;  // V rows per wave instruction
@@ -144,13 +156,23 @@ __global__ __launch_bounds__(256) void decode_attn_k(const DecodeParams p) {
     constexpr int LPK = HD / 8, KPI = 64 / LPK, NI = LK ? 1 : KPW / KPI;
     static_assert(LK || (NI >= 1 && NI <= LPK), "keys per wave vs key rows per instruction");
     const int kl = lane / LPK, dc = LK ? 0 : 8 * (lane % LPK);
-    const KT* kbase = (const KT*)p.k + (int64_t)b * p.k_sb + (int64_t)g * p.k_sg + dc;
+    // r0: the cache row of the chunk's first key: k0 of column b, or (paged)
+    // its place in the pool, from one uniform table load; the entry is
+    // clamped so that a stale table reads a wrong page, never past the pool
+    int r0 = k0;
+    int64_t kb = (int64_t)b * p.k_sb, vb = (int64_t)b * p.v_sb;
+    if constexpr (PAGED) {
+      const int pg = p.page_table[(int64_t)b * p.pt_ld + k0 / KV_PAGE];
+      r0 = min(max(pg, 0), p.n_pages - 1) * KV_PAGE + k0 % KV_PAGE;
+      kb = vb = 0;
+    }
+    const KT* kbase = (const KT*)p.k + kb + (int64_t)g * p.k_sg + dc;
     kpiece kv[NI];
     if constexpr (!LK) {
 #pragma unroll
       for (int i = 0; i < NI; ++i) {
         const int kk = min(wave * KPW + i * KPI + kl, nk - 1);
-        kv[i] = ldk(kbase + (int64_t)(k0 + kk) * p.k_ss);
+        kv[i] = ldk(kbase + (int64_t)(r0 + kk) * p.k_ss);
       }
     }
     // V rows in flight per lane: the whole wave's keys for 1-2 heads per
@@ -161,11 +183,11 @@ __global__ __launch_bounds__(256) void decode_attn_k(const DecodeParams p) {
     static_assert(NV >= 1 && NV % VU == 0, "V rows per instruction vs keys per wave");
     vpair vv[VU];
     const int vg = lane / VL;  // this lane's V row within an instruction (KV8)
-    const KT* vbase = (const KT*)p.v + (int64_t)b * p.v_sb + (int64_t)g * p.v_sg + HP * (lane % VL);
+    const KT* vbase = (const KT*)p.v + vb + (int64_t)g * p.v_sg + HP * (lane % VL);
     auto load_v = [&](int u0) {
 #pragma unroll
       for (int u = 0; u < VU; ++u) {
-        const int kc = min(k0 + wave * KPW + VR * (u0 + u) + vg, k0 + nk - 1);
+        const int kc = min(r0 + wave * KPW + VR * (u0 + u) + vg, r0 + nk - 1);
         vv[u] = *reinterpret_cast<const vpair*>(vbase + (int64_t)kc * p.v_ss);
       }
     };
@@ -195,7 +217,7 @@ __global__ __launch_bounds__(256) void decode_attn_k(const DecodeParams p) {
     // lane; one gather hands lane L < KPW the score of the wave's key L
     float s[RH];
     if constexpr (LK) {
-      const KT* krow = kbase + (int64_t)(k0 + min(wave * KPW + lane, nk - 1)) * p.k_ss;
+      const KT* krow = kbase + (int64_t)(r0 + min(wave * KPW + lane, nk - 1)) * p.k_ss;
 #pragma unroll
       for (int j = 0; j < RH; ++j) s[j] = 0.f;
       // (the branch and the 4-chunk rolled loop keep hipcc from hoisting all
@@ -438,30 +460,35 @@ int decode_kpw_auto(int b, int sk, int nq, int nkv) {
   return grid(16) >= 128 ? 16 : 8;  // b = 1 MHA, 256 keys: 16 -> 7.0 us, 8 -> 7.4 (r4t_kpw)
 }
 
-template <typename T, int HD, int RH, bool KV8>
+template <typename T, int HD, int RH, bool KV8, bool PAGED>
 void launch_rh(const DecodeParams& p, int kpw, hipStream_t s) {
   const int r = p.nq / p.nkv, nhs = (r + RH - 1) / RH;
   const int nsplit = (p.sk + 4 * kpw - 1) / (4 * kpw);
   const dim3 grid(nsplit, p.nkv * nhs, p.b);
-  if (kpw == 64) hipLaunchKernelGGL((decode_attn_k<T, HD, RH, 64, KV8>), grid, dim3(256), 0, s, p);
-  else if (kpw == 16) hipLaunchKernelGGL((decode_attn_k<T, HD, RH, 16, KV8>), grid, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL((decode_attn_k<T, HD, RH, 8, KV8>), grid, dim3(256), 0, s, p);
+  if (kpw == 64) hipLaunchKernelGGL((decode_attn_k<T, HD, RH, 64, KV8, PAGED>), grid, dim3(256), 0, s, p);
+  else if (kpw == 16) hipLaunchKernelGGL((decode_attn_k<T, HD, RH, 16, KV8, PAGED>), grid, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL((decode_attn_k<T, HD, RH, 8, KV8, PAGED>), grid, dim3(256), 0, s, p);
 }
 
-template <typename T, int HD, bool KV8>
+template <typename T, int HD, bool KV8, bool PAGED>
 void launch_kv(const DecodeParams& p, hipStream_t s) {
   const int r = p.nq / p.nkv;
   const int kpw = p.kpw;
-  if (r >= 8) launch_rh<T, HD, 8, KV8>(p, kpw, s);
-  else if (r >= 4) launch_rh<T, HD, 4, KV8>(p, kpw, s);
-  else if (r >= 2) launch_rh<T, HD, 2, KV8>(p, kpw, s);
-  else launch_rh<T, HD, 1, KV8>(p, kpw, s);
+  if (r >= 8) launch_rh<T, HD, 8, KV8, PAGED>(p, kpw, s);
+  else if (r >= 4) launch_rh<T, HD, 4, KV8, PAGED>(p, kpw, s);
+  else if (r >= 2) launch_rh<T, HD, 2, KV8, PAGED>(p, kpw, s);
+  else launch_rh<T, HD, 1, KV8, PAGED>(p, kpw, s);
 }
 
 template <typename T, int HD>
 void launch(const DecodeParams& p, hipStream_t s) {
-  if (p.kv_fp8) launch_kv<T, HD, true>(p, s);
-  else launch_kv<T, HD, false>(p, s);
+  if (p.page_table) {
+    if (p.kv_fp8) launch_kv<T, HD, true, true>(p, s);
+    else launch_kv<T, HD, false, true>(p, s);
+  } else {
+    if (p.kv_fp8) launch_kv<T, HD, true, false>(p, s);
+    else launch_kv<T, HD, false, false>(p, s);
+  }
 }
 
 // Quantising store of new K / V rows into the e4m3 cache (KvStoreParams):

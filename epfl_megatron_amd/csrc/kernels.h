@@ -195,6 +195,11 @@ int flash_attn_waves(int b, int sq, int nq, int hd);
 void flash_attn_fwd(const AttnParams& p, int dt, hipStream_t s);
 
 // ---- flash_decode.hip: one query token per (batch, head) against a KV cache ----
+// Keys per page of a paged KV cache (inference/paged.py holds the same value):
+// the largest decode chunk (4 x 64 keys) and a multiple of the others, so no
+// chunk straddles a page.
+constexpr int KV_PAGE = 256;
+
 struct DecodeParams {
   const void* q;  // query head j of group g at b*q_sb + g*q_sg + (j % r)*q_sh
   const void* k;  // key i of group g at b*k_sb + i*k_ss + g*k_sg
@@ -229,6 +234,13 @@ struct DecodeParams {
   int kv_fp8;
   const float* k_scale;
   const float* v_scale;
+  // paged cache (nullptr: none): device int32 [>= b][pt_ld]; k / v are then a
+  // pool of n_pages pages of KV_PAGE rows (row stride k_ss / v_ss; k_sb / v_sb
+  // unused) and key i of sequence b is pool row page_table[b * pt_ld + i /
+  // KV_PAGE] * KV_PAGE + i % KV_PAGE (entries clamped to [0, n_pages)); sk,
+  // kv_len and window stay logical
+  const int* page_table;
+  int pt_ld, n_pages;
 };
 int flash_decode_kpw(int b, int sk, int nq, int nkv);
 
@@ -286,6 +298,10 @@ struct RaggedTail {
   int* active;
   const int64_t* limit;
   int64_t* tick;
+  // paged cache (nullptr: none), as DecodeParams: an advancing row's slot is
+  // the pool row of its new position
+  const int* page_table;
+  int pt_ld, n_pages;
 };
 void ragged_tail(const void* logits, int64_t ld, int V, int b, int dt, bool sample, int64_t* tokens,
                  int64_t* history, int64_t hist_ld, int64_t hist_cols, const RaggedTail& st,

@@ -30,6 +30,16 @@ with a torch transcription of the tail (``ragged_tail_reference``); the CPU
 tests drive the decoders and the scheduler through it.  PP must be 1; under
 TP the sampling decoder broadcasts TP rank 0's Philox ``(seed, offset)``.
 
+Paged cache (``InferenceParams(..., kv_pages=N)``, ``inference/paged.py``): the
+rows share one pool of pages per layer and ``ip.page_table`` names each row's
+pages.  ``slot`` then holds pool rows: ``prime(..., pages=)`` writes the row's
+table and its first slot, the tail computes the next slot from the table, and
+``release(row)`` sends a finished row to the null page (``slot = 0``, ``kv_len =
+0``, a zero table row) so that the K / V write it still performs on every replay
+cannot land in a page that has gone to another row.  ``ContinuousBatcher``
+reserves all of a request's pages at admission from a ``PagePool`` and makes the
+request wait, in order, while the pool is short.
+
 The reference has no in-flight batching (``megatron/text_generation/
 generation.py`` runs a fixed batch to its longest member); this is an
 MI355X-side addition.
@@ -40,16 +50,19 @@ import torch
 
 from ..parallel import state
 from .hip_graph import broadcast_seed_offset
+from .paged import KV_PAGE, PagePool, pages_for, physical_slots
 
 _TOO_SHORT = "KV cache too short for max_new_tokens"
 
 
 def ragged_tail_reference(tok, tokens, history, hist_idx, pos, slot, kv_len, active, limit, tick,
-                          ctl):
+                          ctl, page_table=None, n_pages=0):
     """Thread 0's bookkeeping of ``ragged_tail_k`` in torch, for the selected
     tokens ``tok [b]`` (any value in parked rows): in place on the state
     tensors; ``ctl[4]`` is the stop id, ``ctl[5]`` receives the number of rows
-    still active."""
+    still active.  ``page_table`` (int32 ``[b, pages_per_row]``, a pool of
+    ``n_pages`` pages): an advancing row's slot becomes the pool row of its new
+    position, the table entry clamped to the pool as the kernel clamps it."""
     tok = tok.view(-1).to(tokens.dtype)
     act = active != 0
     rows = act.nonzero().flatten()
@@ -61,7 +74,12 @@ def ragged_tail_reference(tok, tokens, history, hist_idx, pos, slot, kv_len, act
     go = act & ~done
     active.copy_(go.to(active.dtype))
     pos.add_(go.to(pos.dtype))
-    slot.add_(go.to(slot.dtype))
+    if page_table is None:
+        slot.add_(go.to(slot.dtype))
+    else:
+        pi = (pos // KV_PAGE).clamp(0, page_table.shape[1] - 1)
+        page = page_table.gather(1, pi.view(-1, 1)).view(-1).clamp(0, n_pages - 1)
+        slot.copy_(torch.where(go, page.to(slot.dtype) * KV_PAGE + pos % KV_PAGE, slot))
     kv_len.add_(go.to(kv_len.dtype))
     tick.add_(1)
     ctl[5] = go.sum()
@@ -110,6 +128,13 @@ class RaggedGreedyDecoder:
         self.slot, self.kv_len = z(batch), z(batch, torch.int32)
         self.active = z(batch, torch.int32)
         self.tail_counter = z(1, torch.int32)
+        # paged cache: the table lives next to the state it indexes
+        self.paged = getattr(inference_params, "page_table", None) is not None
+        if self.paged:
+            if batch > self.ip.page_table.shape[0]:
+                raise ValueError("batch exceeds the rows of the page table")
+            self.ip.page_table = self.ip.page_table.to(dev)
+        self._row_pages = {}  # row -> the pages write_table gave it (host copy)
         # [seed, offset0, top_k, vocab_limit, stop_id, rows still active]
         self.ctl = z(6)
         self.stop_id = -1
@@ -141,13 +166,17 @@ class RaggedGreedyDecoder:
                 raise RuntimeError("the ragged tail needs bf16 / fp16 / fp32 logits on the GPU "
                                    "with 16-byte aligned rows")
             ext().ragged_tail(last, *self._state(), self.tail_counter, self.ctl, self.fctl,
-                              self.sample)
+                              self.sample, *self._table())
         else:
-            ragged_tail_reference(self._select(last), *self._state(), self.ctl)
+            ragged_tail_reference(self._select(last), *self._state(), self.ctl, *self._table())
         return logits
 
     def _select(self, last):
         return last.argmax(-1)
+
+    def _table(self):
+        """(page table of the batch's rows, pages of the pool), or () unpaged."""
+        return (self.ip.page_table[:self.batch], self.ip.kv_pages) if self.paged else ()
 
     def _capture(self):
         cur = torch.cuda.current_stream()
@@ -189,25 +218,68 @@ class RaggedGreedyDecoder:
         with torch.no_grad():
             self.ctl[4] = self.stop_id
 
-    def prime(self, row, first_token, position, max_new):
+    def prime(self, row, first_token, position, max_new, pages=None):
         """Start a sequence in ``row``: ``first_token`` is fed at absolute
         ``position`` (= the number of tokens the row's cache column holds) and
         up to ``max_new`` tokens are generated.  Small copies on the current
-        stream; the captured graph is untouched."""
+        stream; the captured graph is untouched.  Paged cache: ``pages`` lists
+        the row's pages (enough for ``position + max_new`` keys; None keeps the
+        table row as it stands, e.g. as written before the prefill); the table
+        row is written, unused entries 0, and the slot is the pool row of
+        ``position``."""
         if not 0 <= row < self.batch:
             raise ValueError(f"row {row} outside the batch of {self.batch}")
         if max_new < 1 or max_new > self.max_new:
             raise ValueError(f"max_new must be in [1, {self.max_new}]")
         if position + max_new > self.ip.max_sequence_len:
             raise ValueError(_TOO_SHORT)
+        if pages is not None and not self.paged:
+            raise ValueError("pages given, but the inference params hold no paged cache")
         with torch.no_grad():
+            slot = position
+            if self.paged:
+                if pages is not None:
+                    self.write_table(row, pages, position + max_new)
+                held = self._row_pages.get(row)  # the host's copy of a row this decoder wrote
+                if held is not None and position // KV_PAGE < len(held):
+                    slot = held[position // KV_PAGE] * KV_PAGE + position % KV_PAGE
+                else:
+                    slot = physical_slots(self.ip.page_table[row],
+                                          torch.tensor(position, device=self.slot.device))
             self.tokens[row] = int(first_token)
             self.pos[row] = position
-            self.slot[row] = position
+            self.slot[row] = slot
             self.kv_len[row] = position + 1
             self.hist_idx[row] = 0
             self.limit[row] = max_new
             self.active[row] = 1
+
+    def write_table(self, row, pages, n_keys):
+        """Row ``row`` of the page table = ``pages`` (which must hold ``n_keys``
+        keys and exclude the null page), the rest 0."""
+        table = self.ip.page_table
+        pages = [int(p) for p in pages]
+        if len(pages) > table.shape[1] or len(pages) < pages_for(n_keys):
+            raise ValueError(f"{len(pages)} pages for {n_keys} keys (pages per row: "
+                             f"{table.shape[1]})")
+        if any(not 0 < p < self.ip.kv_pages for p in pages):
+            raise ValueError(f"pages must lie in [1, {self.ip.kv_pages})")
+        with torch.no_grad():
+            table[row] = torch.tensor(pages + [0] * (table.shape[1] - len(pages)),
+                                      dtype=table.dtype).to(table.device)
+        self._row_pages[row] = pages
+
+    def release(self, row):
+        """Send ``row`` to the null page: inactive, no keys, slot 0 and (paged) a
+        zero table row, on the current stream.  After it the row's former pages
+        may go to another row: the idle row's K / V writes land in page 0."""
+        with torch.no_grad():
+            self.active[row] = 0
+            self.kv_len[row] = 0
+            self.slot[row] = 0
+            if self.paged:
+                self.ip.page_table[row].zero_()
+                self._row_pages.pop(row, None)
 
     def park(self, row):
         """Take ``row`` out of the generation: it keeps its cache slot and
@@ -308,10 +380,10 @@ class RaggedSamplingDecoder(RaggedGreedyDecoder):
             self._new_block()
         self.ticks += 1
 
-    def prime(self, row, first_token, position, max_new):
+    def prime(self, row, first_token, position, max_new, pages=None):
         if self.seed is None:
             self.configure()
-        super().prime(row, first_token, position, max_new)
+        super().prime(row, first_token, position, max_new, pages)
 
     def _select(self, last):
         from ..ops.sampling import sample_ref
@@ -380,6 +452,13 @@ class ContinuousBatcher:
         self.rows = [None] * batch  # request id, first token per busy row
         self.primed = []        # (row, position, max_new) of every prime, for inspection
         self.replays = 0
+        self.paged = getattr(ip, "page_table", None) is not None
+        self.pool = PagePool(ip.kv_pages) if self.paged else None
+        self.row_pages = [None] * batch  # pages held by each busy row
+        self.page_log = []      # (request id, row, pages) of every admission
+        self._idle_since = list(range(batch))  # idle rows are offered the queue oldest first
+        self._idle_tick = batch
+        self.waits = 0          # admissions that found the pool short
 
     def submit(self, prompt_tokens, max_new_tokens):
         """Queue a request; returns its id (= its index in ``run()``'s result)."""
@@ -391,6 +470,12 @@ class ContinuousBatcher:
             raise ValueError(_TOO_SHORT)
         if max_new_tokens < 1 or max_new_tokens - 1 > self.dec.max_new:
             raise ValueError(f"max_new_tokens must be in [1, {self.dec.max_new + 1}]")
+        if self.paged:
+            need = pages_for(prompt.numel() + max_new_tokens)
+            if need > self.pool.n_pages - 1 or need > self.ip.page_table.shape[1]:
+                raise ValueError(f"the request needs {need} KV pages: more than the pool's "
+                                 f"{self.pool.n_pages - 1} usable pages or the "
+                                 f"{self.ip.page_table.shape[1]} pages of a row")
         self.requests.append((prompt, int(max_new_tokens)))
         self.queue.append(len(self.requests) - 1)
         return len(self.requests) - 1
@@ -421,23 +506,50 @@ class ContinuousBatcher:
         return int(last.argmax(-1))
 
     def _admit(self, row):
-        """Fill ``row`` from the queue until a request needs the decoder."""
+        """Fill ``row`` from the queue until a request needs the decoder.
+        Paged: the head request's pages are reserved first; if the pool is
+        short the request stays at the head and the row stays idle."""
         while self.queue:
-            rid = self.queue.popleft()
+            rid = self.queue[0]
             prompt, max_new = self.requests[rid]
+            pages = None
+            if self.paged:
+                pages = self.pool.alloc(pages_for(prompt.numel() + max_new))
+                if pages is None:
+                    self.waits += 1
+                    break
+                self.page_log.append((rid, row, list(pages)))
+                # the table row before the eager prefill, which scatters by it
+                self.dec.write_table(row, pages, prompt.numel() + max_new)
+            self.queue.popleft()
             first = self._prefill(row, prompt)
             if max_new == 1 or (self.dec.stop_id >= 0 and first == self.dec.stop_id):
                 self.results[rid] = [first]  # done on its first token
+                if self.paged:
+                    self._give_back(row, pages)
                 continue
             self.dec.prime(row, first, prompt.numel(), max_new - 1)
             self.primed.append((row, prompt.numel(), max_new - 1))
             self.rows[row] = (rid, first)
+            self.row_pages[row] = pages
             return
         self.rows[row] = None
+
+    def _give_back(self, row, pages):
+        """The order that keeps a parked row from corrupting its successor:
+        ``release`` is enqueued first (the row's later K / V writes go to the
+        null page), then the pages return to the free list."""
+        self.dec.release(row)
+        self.pool.free(pages)
 
     def _collect(self, row, hist_idx):
         rid, first = self.rows[row]
         self.results[rid] = [first] + self.dec.history[row, :hist_idx[row]].tolist()
+        if self.paged:
+            self._give_back(row, self.row_pages[row])
+            self.row_pages[row] = None
+            self._idle_since[row], self._idle_tick = self._idle_tick, self._idle_tick + 1
+        self.rows[row] = None
 
     def run(self):
         """Serve every queued request; token lists in submission order."""
@@ -453,8 +565,18 @@ class ContinuousBatcher:
             if all(active[row] for row in range(self.batch) if self.rows[row] is not None):
                 continue
             hist_idx = dec.hist_idx.tolist()
-            for row in range(self.batch):
-                if self.rows[row] is not None and not active[row]:
+            done = [row for row in range(self.batch)
+                    if self.rows[row] is not None and not active[row]]
+            if not self.paged:
+                for row in done:
                     self._collect(row, hist_idx)
                     self._admit(row)
+                continue
+            # paged: free every finished row's pages first, then offer the queue
+            # to every idle row (a request that waited for pages may now fit)
+            for row in done:
+                self._collect(row, hist_idx)
+            idle = [row for row in range(self.batch) if self.rows[row] is None]
+            for row in sorted(idle, key=self._idle_since.__getitem__):
+                self._admit(row)
         return [self.results[i] for i in range(len(self.requests))]

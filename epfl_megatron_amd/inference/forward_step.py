@@ -20,7 +20,22 @@ from .communication import device, recv_from_prev_pipeline_rank_, send_to_next_p
 
 class InferenceParams:
 
-    def __init__(self, max_batch_size, max_sequence_len):
+    def __init__(self, max_batch_size, max_sequence_len, kv_pages=None, table_device=None):
+        """``kv_pages = N``: a paged cache (``inference/paged.py``), per layer one
+        pool of ``N`` pages of ``KV_PAGE`` keys for K and one for V, and
+        ``page_table`` (int32 ``[max_batch_size, pages_per_row]``, zero-filled:
+        every entry at the null page 0) on ``table_device`` (default: the
+        inference device).  None: a full-capacity cache column per row."""
+        self.kv_pages = self.page_table = None
+        if kv_pages is not None:
+            from .paged import pages_for
+            if kv_pages < 2:
+                raise ValueError("kv_pages must be >= 2: page 0 is the null page")
+            self.kv_pages = int(kv_pages)
+            self.pages_per_row = pages_for(max_sequence_len)
+            self.page_table = torch.zeros(max_batch_size, self.pages_per_row, dtype=torch.int32,
+                                          device=table_device if table_device is not None
+                                          else device())
         self.max_sequence_len = max_sequence_len
         self.max_batch_size = max_batch_size
         self.sequence_len_offset = 0
@@ -48,6 +63,9 @@ class InferenceParams:
 
     def swap_key_value_dict(self, batch_idx):
         """Reorder the cached batch rows (beam search keeps the best beams)."""
+        if self.page_table is not None:
+            raise NotImplementedError("swap_key_value_dict (beam search) reorders cache columns, "
+                                      "which a paged KV cache does not have; use kv_pages=None")
         if not self.key_value_memory_dict:
             raise ValueError("should not swap when dict in empty")
         for layer, (k, v) in self.key_value_memory_dict.items():

@@ -83,6 +83,14 @@ def _pp_stage():
     return state.is_pipeline_first_stage(), state.is_pipeline_last_stage()
 
 
+def _check_unpaged(inference_params, who):
+    if getattr(inference_params, "page_table", None) is not None:
+        raise NotImplementedError(
+            f"{who} moves the batch in lockstep (one cache slot for all rows) and is not "
+            "paged: a paged KV cache is served by the ragged decoders of "
+            "inference/continuous.py; use kv_pages=None")
+
+
 class GraphedDecodeForward:
     """The single-token model forward of ``ForwardStep`` (``--inference_hip_graph``):
     inputs are copied into static tensors, the cache slot / key count are
@@ -92,6 +100,7 @@ class GraphedDecodeForward:
     valid until the next call."""
 
     def __init__(self, model, inference_params, batch, capture=None):
+        _check_unpaged(inference_params, "GraphedDecodeForward")
         self.model = model
         self.ip = inference_params
         self.capture = torch.cuda.is_available() if capture is None else capture
@@ -160,6 +169,7 @@ class GraphedGreedyDecoder:
 
     def __init__(self, model, inference_params, batch, max_new_tokens):
         _check_supported()
+        _check_unpaged(inference_params, type(self).__name__)
         self.model = model
         self.ip = inference_params
         self.batch = batch

@@ -345,6 +345,92 @@ class ParallelAttention(MegatronModule):
         return (torch.empty(shape, dtype=self.params_dtype, device=device),
                 torch.empty(shape, dtype=self.params_dtype, device=device))
 
+    def _kv_memory(self, ip, device):
+        """This layer's (K, V) cache on ``ip``, allocated on first use: a column
+        per row, or with ``ip.kv_pages`` one pool ``[kv_pages * KV_PAGE, 1, nkv,
+        hd]`` each (``inference/paged.py``)."""
+        if self.layer_number not in ip.key_value_memory_dict:
+            if getattr(ip, "page_table", None) is not None:
+                from ..inference.paged import KV_PAGE
+                shape = (ip.kv_pages * KV_PAGE, 1)
+            else:
+                shape = (ip.max_sequence_len, ip.max_batch_size)
+            ip.key_value_memory_dict[self.layer_number] = self._allocate_kv(*shape, device)
+        return ip.key_value_memory_dict[self.layer_number]
+
+    def _paged_forward(self, q, k, v, kmem, vmem, attention_mask, ip):
+        """``_inference_forward`` over a paged cache (16-bit or FP8 pools).  A
+        decode step with device slots writes row ``m``'s K / V at the pool row
+        ``ip.device_offset[m]`` (kept physical by the ragged decoders) and reads
+        through ``ip.page_table``; the whole-prompt prefill of one row scatters
+        its rows to the pool by the row's table, on the device, and attends
+        over the fresh K and V.  Nothing else is supported."""
+        from ..inference.paged import KV_PAGE, physical_slots
+        s0, b0 = ip.sequence_len_offset, ip.batch_size_offset
+        sq, b = q.shape[:2]
+        fp8 = kmem.dtype == torch.uint8
+        sc = self._kv_scales(ip, q.device) if fp8 else None
+        table = ip.page_table[b0:b0 + b]
+        if getattr(ip, "device_offset", None) is not None and sq == 1:
+            if q.is_cuda and not (use_native(q) and q.shape[-1] in (64, 128)):
+                raise NotImplementedError("hipGraph decode needs the native decode attention "
+                                          "kernel (GPU, bf16/fp16, head_dim 64 or 128)")
+            slots = ip.device_offset
+            if slots.numel() != b:
+                raise NotImplementedError(
+                    "a paged KV cache needs one cache slot per row (the ragged decoders of "
+                    "inference/continuous.py): the lockstep decoders of inference/hip_graph.py "
+                    "are not paged; use kv_pages=None")
+            if fp8 and fp8_kv.store_native_ok(k) and fp8_kv.store_native_ok(v):
+                # the pool as a stride-0 batch view: row m lands at slots[m]
+                fp8_kv.store(k, v, kmem.expand(-1, b, -1, -1), vmem.expand(-1, b, -1, -1), sc,
+                             slot_t=slots)
+            elif fp8:
+                kmem[slots, 0] = fp8_kv.quantize(k[0], sc[0])
+                vmem[slots, 0] = fp8_kv.quantize(v[0], sc[1])
+            else:
+                kmem[slots, 0] = k[0]
+                vmem[slots, 0] = v[0]
+            o = flash_decode_cached(q.transpose(0, 1), kmem.transpose(0, 1), vmem.transpose(0, 1),
+                                    ip.device_kv_len, window=self._window(ip.max_sequence_len),
+                                    kv_scale=sc, page_table=table, capacity=ip.max_sequence_len)
+            return o.transpose(0, 1).reshape(sq, b, -1)
+        why = None
+        if sq == 1:
+            why = "a decode step without device slots (the eager KV-cached loop)"
+        elif s0 > 0:
+            why = "a prefill that continues a cached sequence (sequence_len_offset > 0)"
+        elif b > 1:
+            why = "a prefill of more than one row"
+        elif fp8 and _FP8_KV_CALIBRATE:
+            why = "prompt calibration of the FP8 KV scales (--inference_fp8_kv_calibrate)"
+        if why is not None:
+            raise NotImplementedError(f"paged KV cache: {why} is not supported (only the "
+                                      "whole-prompt prefill of one row and the ragged decode "
+                                      "step are); use kv_pages=None")
+        # the prompt's rows go to the pool rows its table names: device-side indices
+        # (computed by the first layer of a prefill and shared by the others: the
+        # table's version counter moves with every write to it)
+        key = (b0, sq, id(ip.page_table), ip.page_table._version)
+        if getattr(ip, "_prefill_slots", (None,))[0] != key:
+            ip._prefill_slots = (key, physical_slots(table[0], torch.arange(sq, device=k.device)))
+        idx = ip._prefill_slots[1]
+        if fp8 and fp8_kv.store_native_ok(k) and fp8_kv.store_native_ok(v):
+            for p0 in range(0, sq, KV_PAGE):  # a page's rows are consecutive in the pool
+                fp8_kv.store(k[p0:p0 + KV_PAGE], v[p0:p0 + KV_PAGE], kmem, vmem, sc,
+                             slot_t=idx[p0:p0 + 1])
+        elif fp8:
+            kmem.index_copy_(0, idx, fp8_kv.quantize(k, sc[0]))
+            vmem.index_copy_(0, idx, fp8_kv.quantize(v, sc[1]))
+        else:
+            kmem.index_copy_(0, idx, k)
+            vmem.index_copy_(0, idx, v)
+        if self.use_flash_attn:
+            o = flash_attn_func(q.transpose(0, 1), k.transpose(0, 1), v.transpose(0, 1),
+                                causal=True, window=self._window(sq))
+            return o.transpose(0, 1).reshape(sq, b, -1)
+        return self.core_attention(q, self._expand_kv(k), self._expand_kv(v), attention_mask)
+
     def _kv_scales(self, ip, device):
         """This layer's FP8 cache scales (fp32 [2, nkv_per_tp], 1.0 until set),
         kept on the inference params next to the cache."""
@@ -466,14 +552,13 @@ class ParallelAttention(MegatronModule):
             rope = None
         q, k, v = self._split_qkv(mixed)
         sq, b = q.shape[:2]
-        if self.layer_number not in ip.key_value_memory_dict:
-            ip.key_value_memory_dict[self.layer_number] = self._allocate_kv(
-                ip.max_sequence_len, ip.max_batch_size, mixed.device)
-        kmem, vmem = ip.key_value_memory_dict[self.layer_number]
+        kmem, vmem = self._kv_memory(ip, mixed.device)
         if rope is not None:
             # Rotate with the true positions BEFORE caching (fixes D1).
             q = apply_rope_ref(q, rope[0], rope[1], position_ids, offset=s0)
             k = apply_rope_ref(k, rope[0], rope[1], position_ids, offset=s0)
+        if getattr(ip, "page_table", None) is not None:
+            return self._paged_forward(q, k, v, kmem, vmem, attention_mask, ip)
         if kmem.dtype == torch.uint8:
             return self._fp8_kv_forward(q, k, v, kmem, vmem, attention_mask, ip)
         if getattr(ip, "device_offset", None) is not None and sq == 1:
@@ -624,12 +709,22 @@ class ParallelTransformerLayer(MegatronModule):
         x = hidden_states.reshape(b, H)
         if not x.is_contiguous():
             x = x.contiguous()
-        if sa.layer_number not in ip.key_value_memory_dict:
-            ip.key_value_memory_dict[sa.layer_number] = sa._allocate_kv(
-                ip.max_sequence_len, ip.max_batch_size, x.device)
-        kmem, vmem = ip.key_value_memory_dict[sa.layer_number]
+        kmem, vmem = sa._kv_memory(ip, x.device)
         b0, s0 = ip.batch_size_offset, ip.sequence_len_offset
-        kc, vc = kmem[:, b0:b0 + b], vmem[:, b0:b0 + b]
+        table = getattr(ip, "page_table", None)
+        if table is not None:
+            # paged cache (inference/paged.py): the pool as a stride-0 batch view,
+            # so that the QKV epilogue writes row m at the pool row device_offset[m]
+            if getattr(ip, "device_offset", None) is None or ip.device_offset.numel() != b:
+                raise NotImplementedError(
+                    "paged KV cache: a decode step needs one device cache slot per row (the "
+                    "ragged decoders of inference/continuous.py); the eager loop and the "
+                    "lockstep decoders of inference/hip_graph.py are not paged; use "
+                    "kv_pages=None")
+            table = table[b0:b0 + b]
+            kc, vc = kmem.expand(-1, b, -1, -1), vmem.expand(-1, b, -1, -1)
+        else:
+            kc, vc = kmem[:, b0:b0 + b], vmem[:, b0:b0 + b]
         # FP8 KV cache: the QKV epilogue quantises k / v with these scales
         kvs = sa._kv_scales(ip, x.device) if kmem.dtype == torch.uint8 else None
         cos, sin = sa._rope(x.device)
@@ -671,7 +766,11 @@ class ParallelTransformerLayer(MegatronModule):
                                     ip.device_offset if graph else None, 0 if graph else s0,
                                     pq is not None, sq, *(() if kvs is None else (kvs,)))
         q4 = q.view(b, 1, ng * r, hd)
-        if graph:
+        if table is not None:
+            o = flash_decode_cached(q4, kmem.transpose(0, 1), vmem.transpose(0, 1),
+                                    ip.device_kv_len, window=sa._window(ip.max_sequence_len),
+                                    kv_scale=kvs, page_table=table, capacity=ip.max_sequence_len)
+        elif graph:
             o = flash_decode_cached(q4, kc.transpose(0, 1), vc.transpose(0, 1), ip.device_kv_len,
                                     window=sa._window(kc.shape[0]), kv_scale=kvs)
         elif kvs is not None:

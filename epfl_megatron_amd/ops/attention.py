@@ -151,34 +151,69 @@ class _FlashQKVPackedFn(torch.autograd.Function):
         return dqkv5.view(s, b, -1), None, None, None, None, None, None, None, None, None, None
 
 
-def _flash_decode(q, k, v, scale, kv_len=None, window=0, kv_scale=None):
+def _flash_decode(q, k, v, scale, kv_len=None, window=0, kv_scale=None, page_table=None, sk=None):
     """sq == 1 against a KV cache (generation): split-key decode kernel
     (``csrc/flash_decode.hip``); no autograd.  ``kv_len``: optional device
     int32 tensor with the number of valid keys (k / v then span the whole
     cache; the launch does not depend on the step, for hipGraph capture).
     ``window``: only the last ``window`` valid keys count (0: all).
     ``kv_scale``: fp32 ``[2, nkv]`` when k / v are an FP8 cache (uint8 e4m3fn
-    bytes, ``ops/fp8_kv.py``)."""
+    bytes, ``ops/fp8_kv.py``).  ``page_table``: k / v are the pool of a paged
+    cache ``[1, n_pages * KV_PAGE, nkv, d]`` and ``sk`` the logical capacity."""
     b, _, nq, d = q.shape
-    sk, nkv = k.shape[1], k.shape[2]
+    nkv = k.shape[2]
+    if page_table is None:
+        sk = k.shape[1]
     r = nq // nkv
     out = torch.empty(b, 1, nq, d, dtype=q.dtype, device=q.device)
     ext().flash_decode(q, k, v, out, b, sk, nq, nkv, d, list(_bsnd_strides(q, r)),
                        list(_bsnd_strides(k, 1)[:3]), list(_bsnd_strides(v, 1)[:3]),
                        [out.stride(0), out.stride(1), out.stride(2)], float(scale), kv_len,
-                       window=int(window), kv_scale=kv_scale)
+                       window=int(window), kv_scale=kv_scale, page_table=page_table)
     return out
 
 
-def flash_decode_cached(q, k, v, kv_len, softmax_scale=None, window=0, kv_scale=None):
+def flash_decode_cached(q, k, v, kv_len, softmax_scale=None, window=0, kv_scale=None,
+                        page_table=None, capacity=None):
     """One query row per sequence against a whole KV cache ``k / v [b, smax,
     nkv, d]`` of which the first ``kv_len`` (device int32) keys are valid
     (with ``window``: the last ``window`` of those).  ``kv_len`` None: all
     ``smax`` keys are valid.  ``kv_scale``: fp32 ``[2, nkv]`` when k / v are an
     FP8 cache (uint8 e4m3fn bytes, ``ops/fp8_kv.py``).  A ``kv_len`` of ``b >
     1`` elements holds one length per sequence (ragged decode): row ``i`` sees
-    the keys ``[max(0, n_i - window), n_i)``, none (zeros) at ``n_i == 0``."""
+    the keys ``[max(0, n_i - window), n_i)``, none (zeros) at ``n_i == 0``.
+
+    ``page_table`` (int32 ``[>= b, pages_per_row]``): a paged cache
+    (``inference/paged.py``).  k / v are then the pool ``[1, n_pages * KV_PAGE,
+    nkv, d]``, key ``j`` of row ``i`` is pool row ``page_table[i, j // KV_PAGE] *
+    KV_PAGE + j % KV_PAGE``, ``kv_len`` is required and ``capacity`` (default
+    ``pages_per_row * KV_PAGE``) is the logical cache length that sizes the
+    launch as ``smax`` does without a table."""
     _check_window(window, True)
+    if page_table is not None:
+        from ..inference.paged import KV_PAGE, gather_rows
+        if kv_len is None:
+            raise ValueError("a page_table needs kv_len (the keys each row's pages hold)")
+        if capacity is None:
+            capacity = page_table.shape[1] * KV_PAGE
+        if capacity > page_table.shape[1] * KV_PAGE:
+            raise ValueError("capacity exceeds the page_table's pages per row")
+        if not use_native(q):
+            # gather each row's pages into the contiguous cache and take the reference
+            lens = kv_len.reshape(-1).tolist()
+            lens = lens * q.shape[0] if len(lens) == 1 else lens
+            rows = []
+            for i in range(q.shape[0]):
+                n = min(lens[i], capacity)
+                if n <= 0:
+                    rows.append(torch.zeros_like(q[i:i + 1]))
+                    continue
+                ki, vi = (gather_rows(t[0], page_table[i], n)[None] for t in (k, v))
+                rows.append(flash_decode_cached(q[i:i + 1], ki, vi, None, softmax_scale, window,
+                                                kv_scale))
+            return torch.cat(rows, 0)
+        scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(q.shape[-1])
+        return _flash_decode(q, k, v, scale, kv_len, window, kv_scale, page_table, int(capacity))
     if not use_native(q):
         if kv_len is not None and q.shape[0] > 1 and kv_len.numel() == q.shape[0]:
             rows = []

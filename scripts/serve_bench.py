@@ -21,6 +21,11 @@ GraphedGreedyDecoder / GraphedSamplingDecoder, each group running to its longest
 member.  Reports useful tokens/s (tokens a request asked for, prefill time
 included) for both; with a prompt-length range the baseline is "not possible".
 
+--kv_pages N (with --continuous): the batcher over a paged KV cache of N pages
+of 256 keys (inference/paged.py); reports how often an admission waited for
+pages and the peak pages in use.  --paged_cost: the same requests, seed and
+batch through the unpaged and the paged batcher in one process, alternating.
+
 --ragged_cost: what per-row state costs a uniform batch: RaggedGreedyDecoder
 against GraphedGreedyDecoder from the same prefilled cache, --reps repetitions
 each, alternating; the spread of the lockstep decoder's repetitions is the margin.
@@ -28,7 +33,8 @@ each, alternating; the spread of the lockstep decoder's repetitions is the margi
 Usage: python scripts/serve_bench.py [--batches 1,8,32] [--graph]
        [--top_k K | --top_p P] [--temperature T]
        [--continuous [--requests N] [--prompt_range LO,HI] [--gen_range LO,HI]
-        [--poll_every 1,4,16]] [--ragged_cost [--reps 3]]
+        [--poll_every 1,4,16] [--kv_pages N] [--capacity C]] [--ragged_cost [--reps 3]]
+       [--paged_cost [--reps 3] [--kv_pages N]]
 """
 import argparse
 import json
@@ -70,8 +76,19 @@ def main():
     ap.add_argument("--ragged_cost", action="store_true",
                     help="RaggedGreedyDecoder against GraphedGreedyDecoder on a uniform batch")
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--only", choices=["lockstep", "ragged"], default=None,
-                    help="--ragged_cost: run one of the two decoders (a per-kernel profile of each)")
+    ap.add_argument("--only", choices=["lockstep", "ragged", "unpaged", "paged"], default=None,
+                    help="--ragged_cost / --paged_cost: run one of the two sides (a per-kernel "
+                         "profile of each)")
+    ap.add_argument("--kv_pages", default="",
+                    help="--continuous: pages of the paged KV cache (InferenceParams kv_pages), one "
+                         "value or one per --batches entry, 0: unpaged; --paged_cost: the paged "
+                         "side's pages (default: enough that nothing waits)")
+    ap.add_argument("--capacity", type=int, default=0,
+                    help="--continuous / --paged_cost: cache capacity per row (default: the longest "
+                         "request)")
+    ap.add_argument("--paged_cost", action="store_true",
+                    help="the same requests through the unpaged and the paged ContinuousBatcher, "
+                         "alternating, --reps repetitions each")
     a = ap.parse_args()
     sampling = a.top_k > 0 or a.top_p > 0.0 or a.temperature != 1.0
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=os.environ.get("MASTER_PORT", "29561"),
@@ -112,6 +129,8 @@ def main():
     initialize_megatron(finetune.extra_args, {"tokenizer_type": "NullTokenizer"}, args_list=argv)
     model = get_model(finetune.model_provider, ModelType.encoder_or_decoder, wrap_with_ddp=False)
     m = model[0].eval()
+    if a.paged_cost:
+        return paged_cost(a, m)
     if a.continuous:
         return continuous(a, m, sampling, skw)
     if a.ragged_cost:
@@ -180,9 +199,11 @@ def continuous(a, m, sampling, skw):
     from epfl_megatron_amd.inference.hip_graph import GraphedGreedyDecoder, GraphedSamplingDecoder
     from epfl_megatron_amd.ops.sampling import sample_fused
     (plo, phi), (glo, ghi) = ([int(x) for x in r.split(",")] for r in (a.prompt_range, a.gen_range))
-    cap = phi + ghi
+    cap = max(phi + ghi, a.capacity)
+    pages = [int(x) for x in a.kv_pages.split(",")] if a.kv_pages else [0]
     res = []
-    for B in [int(x) for x in a.batches.split(",")]:
+    for bi, B in enumerate([int(x) for x in a.batches.split(",")]):
+        kvp = pages[min(bi, len(pages) - 1)]
         n = a.requests or 4 * B
         g = torch.Generator().manual_seed(a.seed)
         plens = torch.randint(plo, phi + 1, (n,), generator=g).tolist()
@@ -190,10 +211,10 @@ def continuous(a, m, sampling, skw):
         prompts = [torch.randint(0, 32000, (p,), generator=g) for p in plens]
         useful = sum(gens)
         base = {"mode": "continuous", "batch": B, "requests": n, "prompt_range": [plo, phi],
-                "gen_range": [glo, ghi], "useful_tokens": useful,
-                "sampling": dict(skw) if sampling else "greedy"}
+                "gen_range": [glo, ghi], "useful_tokens": useful, "capacity": cap,
+                "kv_pages": kvp, "sampling": dict(skw) if sampling else "greedy"}
         for poll in [int(x) for x in a.poll_every.split(",")]:
-            ip = InferenceParams(B, cap)
+            ip = InferenceParams(B, cap, kv_pages=kvp or None)
             dec = None
             if sampling:
                 dec = RaggedSamplingDecoder(m, ip, B, ghi, vocab_size=32000)
@@ -202,17 +223,21 @@ def continuous(a, m, sampling, skw):
             for p in prompts[:B]:  # warm-up: the capture, the allocator, the prefill kernels
                 cb.submit(p, 4)
             cb.run()
-            warm = cb.replays
+            warm, waits0 = cb.replays, cb.waits
+            if kvp:
+                cb.pool.peak = cb.pool.in_use
             for p, gn in zip(prompts, gens):
                 cb.submit(p, gn)
             out, dt = _timed(cb.run)
             assert [len(o) for o in out[-n:]] == gens and cb.dec.captures == 1
             r = dict(base, poll_every=poll, replays=cb.replays - warm, seconds=round(dt, 3),
-                     continuous_tokens_per_s=round(useful / dt, 1))
+                     continuous_tokens_per_s=round(useful / dt, 1), kv_gib=_kv_gib(ip))
+            if kvp:
+                r.update(admission_waits=cb.waits - waits0, peak_pages=cb.pool.peak)
             if plo != phi:
                 r["static_tokens_per_s"] = "not possible"
             res.append(r)
-        if plo == phi:  # the lockstep baseline: groups of B, each to its longest member
+        if plo == phi and not kvp:  # the lockstep baseline: groups of B, each to its longest member
             ip = InferenceParams(B, cap)
             pos = torch.arange(cap, device="cuda")[None].expand(B, -1)
             dec = GraphedSamplingDecoder(m, ip, B, ghi, vocab_size=32000) if sampling else \
@@ -239,6 +264,67 @@ def continuous(a, m, sampling, skw):
                          static_replays=steps)
         for r in res[-len(a.poll_every.split(",")):]:
             print(json.dumps(r), flush=True)
+    return res
+
+
+def _kv_gib(ip):
+    """GiB of K / V cache the layers allocated on ``ip``."""
+    return round(sum(t.numel() * t.element_size() for kv in ip.key_value_memory_dict.values()
+                     for t in kv) / 2 ** 30, 3)
+
+
+def paged_cost(a, m):
+    """--paged_cost: the same seeded request list through the unpaged and the
+    paged ContinuousBatcher in one process, alternating, --reps timed
+    repetitions each after a warm-up; the page count is large enough that no
+    admission waits, so the difference is the indirection alone."""
+    import torch
+    from epfl_megatron_amd.inference import ContinuousBatcher
+    from epfl_megatron_amd.inference.forward_step import InferenceParams
+    from epfl_megatron_amd.inference.paged import pages_for
+    (plo, phi), (glo, ghi) = ([int(x) for x in r.split(",")] for r in (a.prompt_range, a.gen_range))
+    cap = max(phi + ghi, a.capacity)
+    poll = int(a.poll_every.split(",")[0])
+    res = []
+    for B in [int(x) for x in a.batches.split(",")]:
+        n = a.requests or 4 * B
+        g = torch.Generator().manual_seed(a.seed)
+        plens = torch.randint(plo, phi + 1, (n,), generator=g).tolist()
+        gens = torch.randint(glo, ghi + 1, (n,), generator=g).tolist()
+        prompts = [torch.randint(0, 32000, (p,), generator=g) for p in plens]
+        useful = sum(gens)
+        kvp = int(a.kv_pages) if a.kv_pages else B * pages_for(cap) + 1
+        cbs, secs, outs = {}, {}, {}
+        for name in ([a.only] if a.only else ["unpaged", "paged"]):
+            ip = InferenceParams(B, cap, kv_pages=kvp if name == "paged" else None)
+            cb = ContinuousBatcher(m, ip, B, cap, poll_every=poll, max_new_tokens=ghi)
+            for p in prompts[:B]:  # warm-up: the capture, the allocator, the prefill kernels
+                cb.submit(p, 4)
+            cb.run()
+            cbs[name], secs[name] = cb, []
+        for rep in range(a.reps):
+            for name, cb in cbs.items():
+                for p, gn in zip(prompts, gens):
+                    cb.submit(p, gn)
+                out, dt = _timed(cb.run)
+                assert [len(o) for o in out[-n:]] == gens and cb.dec.captures == 1
+                secs[name].append(round(dt, 4))
+                outs[name] = out[-n:]
+        r = {"mode": "paged_cost", "batch": B, "requests": n, "prompt_range": [plo, phi],
+             "gen_range": [glo, ghi], "capacity": cap, "kv_pages": kvp, "poll_every": poll,
+             "useful_tokens": useful}
+        for name, cb in cbs.items():
+            r[name + "_seconds"] = secs[name]
+            r[name + "_tokens_per_s"] = [round(useful / t, 1) for t in secs[name]]
+            r[name + "_kv_gib"] = _kv_gib(cb.ip)
+        if not a.only:
+            mean = {k: sum(v) / len(v) for k, v in secs.items()}
+            r.update(unpaged_spread_s=round(max(secs["unpaged"]) - min(secs["unpaged"]), 4),
+                     paged_minus_unpaged_s=round(mean["paged"] - mean["unpaged"], 4),
+                     paged_minus_unpaged_pct=round(100 * (mean["paged"] / mean["unpaged"] - 1), 2),
+                     admission_waits=cbs["paged"].waits, same_tokens=outs["paged"] == outs["unpaged"])
+        print(json.dumps(r), flush=True)
+        res.append(r)
     return res
 
 
