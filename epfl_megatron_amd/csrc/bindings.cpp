@@ -476,7 +476,8 @@ ema::AttnParams make_attn(const at::Tensor& q, const at::Tensor& k, const at::Te
                           int64_t sk, int64_t nq, int64_t nkv, int64_t hd,
                           const std::vector<int64_t>& qs, const std::vector<int64_t>& ks,
                           const std::vector<int64_t>& vs, const std::vector<int64_t>& os,
-                          bool causal, double scale, bool lse_view = false) {
+                          bool causal, double scale, bool lse_view = false,
+                          int64_t pool_rows = 0) {
   TORCH_CHECK(qs.size() == 4 && ks.size() == 3 && vs.size() == 3 && os.size() == 3, "bad strides");
   TORCH_CHECK(q.scalar_type() == k.scalar_type() && q.scalar_type() == v.scalar_type() &&
               q.scalar_type() == out.scalar_type(), "q/k/v/out dtype mismatch");
@@ -500,9 +501,12 @@ ema::AttnParams make_attn(const at::Tensor& q, const at::Tensor& k, const at::Te
   const int64_t qspan = (b - 1) * qs[0] + (sq - 1) * qs[1] + (nkv - 1) * qs[2] + (r - 1) * qs[3] + hd;
   TORCH_CHECK(q.storage_offset() + qspan <= (int64_t)(q.storage().nbytes() / q.element_size()),
               "q strides exceed storage");
-  TORCH_CHECK(k.storage_offset() + span(b, sk, nkv, ks[0], ks[1], ks[2], hd) <=
+  // (paged keys, pool_rows > 0: k / v are one pool of that many rows, every
+  // one of which a table entry can select; the batch stride is unused)
+  const int64_t kb = pool_rows > 0 ? 1 : b, krows = pool_rows > 0 ? pool_rows : sk;
+  TORCH_CHECK(k.storage_offset() + span(kb, krows, nkv, ks[0], ks[1], ks[2], hd) <=
               (int64_t)(k.storage().nbytes() / k.element_size()), "k strides exceed storage");
-  TORCH_CHECK(v.storage_offset() + span(b, sk, nkv, vs[0], vs[1], vs[2], hd) <=
+  TORCH_CHECK(v.storage_offset() + span(kb, krows, nkv, vs[0], vs[1], vs[2], hd) <=
               (int64_t)(v.storage().nbytes() / v.element_size()), "v strides exceed storage");
   TORCH_CHECK(out.storage_offset() + span(b, sq, nq, os[0], os[1], os[2], hd) <=
               (int64_t)(out.storage().nbytes() / out.element_size()), "out strides exceed storage");
@@ -578,13 +582,50 @@ void flash_attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& 
                     const c10::optional<at::Tensor>& rope_cos,
                     const c10::optional<at::Tensor>& rope_sin,
                     const c10::optional<at::Tensor>& rope_pos,
-                    const c10::optional<at::Tensor>& docs, int64_t window) {
+                    const c10::optional<at::Tensor>& docs, int64_t window,
+                    const c10::optional<at::Tensor>& page_table, int64_t waves, int64_t kv2) {
   check_gpu(q, "q");
-  auto p = make_attn(q, k, v, out, lse, b, sq, sk, nq, nkv, hd, qs, ks, vs, os, causal, scale);
+  TORCH_CHECK(waves == 0 || waves == 4 || waves == 8, "waves must be 0 (automatic), 4 or 8");
+  TORCH_CHECK(kv2 >= -1 && kv2 <= 1, "kv2 must be -1 (automatic), 0 or 1");
+  TORCH_CHECK(kv2 != 1 || (hd == 128 && waves == 0),
+              "kv2 = 1 (the split-key form) needs head_dim 128 and waves = 0");
+  // paged keys: k / v are the pool [1, n_pages * KV_PAGE, nkv, hd] (strides ks /
+  // vs = (unused, row, group)), page_table int32 [>= b, pt_ld]; make_attn then
+  // validates the pool as one batch row of n_pages * KV_PAGE keys
+  int64_t pt_ld = 0, n_pages = 0;
+  const bool paged = page_table.has_value() && page_table->defined();
+  if (paged) {
+    TORCH_CHECK(page_table->scalar_type() == at::kInt, "page_table must be an int32 tensor");
+    TORCH_CHECK(page_table->is_cuda() && page_table->device() == q.device(),
+                "page_table must be on q's device");
+    TORCH_CHECK(page_table->dim() == 2 && page_table->is_contiguous() && page_table->size(0) >= b &&
+                page_table->size(1) >= 1, "page_table must be 2-D contiguous [>= b, pages_per_row]");
+    pt_ld = page_table->size(1);
+    TORCH_CHECK(sk <= pt_ld * ema::KV_PAGE, "sk exceeds the page_table's ", pt_ld, " pages of ",
+                ema::KV_PAGE, " keys per row");
+    TORCH_CHECK(causal, "a page_table needs causal attention");
+    TORCH_CHECK(!(rope_cos.has_value() && rope_cos->defined()),
+                "rope_cos cannot be combined with a page_table");
+    TORCH_CHECK(!(docs.has_value() && docs->defined()), "docs cannot be combined with a page_table");
+    TORCH_CHECK(k.dim() == 4 && v.dim() == 4 && k.size(0) == 1 && v.size(0) == 1 &&
+                k.size(1) == v.size(1), "paged k / v must be pool views [1, rows, nkv, hd]");
+    n_pages = k.size(1) / ema::KV_PAGE;
+    TORCH_CHECK(n_pages >= 1 && k.size(1) == n_pages * ema::KV_PAGE && k.size(1) < (1ll << 31),
+                "the k / v pool must hold n_pages * ", ema::KV_PAGE, " rows");
+    TORCH_CHECK(k.is_cuda() && v.is_cuda() && k.device() == q.device() && v.device() == q.device(),
+                "k / v on another device");
+  }
+  auto p = make_attn(q, k, v, out, lse, b, sq, sk, nq, nkv, hd, qs, ks, vs, os, causal, scale, false,
+                     n_pages * ema::KV_PAGE);
+  if (paged) {
+    p.page_table = page_table->data_ptr<int>();
+    p.pt_ld = (int)pt_ld;
+    p.n_pages = (int)n_pages;
+  }
   set_rope(p, rope_cos, rope_sin, rope_pos);
   set_docs(p, docs);
   set_window(p, window);
-  ema::flash_attn_fwd(p, dtype_code(q), cur_stream());
+  ema::flash_attn_fwd(p, dtype_code(q), cur_stream(), (int)waves, (int)kv2);
 }
 
 // One ring-attention step (parallel/context.py): attention of q over this K/V
@@ -1553,7 +1594,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("lse"), py::arg("b"), py::arg("sq"), py::arg("sk"), py::arg("nq"), py::arg("nkv"),
         py::arg("hd"), py::arg("qs"), py::arg("ks"), py::arg("vs"), py::arg("os"),
         py::arg("causal"), py::arg("scale"), py::arg("rope_cos"), py::arg("rope_sin"),
-        py::arg("rope_pos"), py::arg("docs"), py::arg("window") = 0);
+        py::arg("rope_pos"), py::arg("docs"), py::arg("window") = 0,
+        py::arg("page_table") = py::none(), py::arg("waves") = 0, py::arg("kv2") = -1);
   m.def("flash_attn_fwd_merge", &flash_attn_fwd_merge, py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("o32"), py::arg("lse"), py::arg("b"), py::arg("sq"), py::arg("sk"), py::arg("nq"),
         py::arg("nkv"), py::arg("hd"), py::arg("qs"), py::arg("ks"), py::arg("vs"),

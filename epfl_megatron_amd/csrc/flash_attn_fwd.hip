@@ -35,7 +35,17 @@
 // Fused RoPE (p.rope_cos set): Q is rotated in registers right after its load
 // and written back in place (only this workgroup reads those rows), so the
 // backward sees rotated Q; K is rotated by a k-only pre-pass (rope.hip).
+//
+// Paged keys (PAGED, p.page_table set: the continued prefill of a paged KV
+// cache, inference/paged.py): k / v are a pool of pages of KV_PAGE keys and key
+// i of batch row b is pool row table[b][i / KV_PAGE] * KV_PAGE + i % KV_PAGE.
+// KT divides KV_PAGE, so a tile lies in one page: its page is one uniform
+// (scalar) table load per tile and only the DMA's source row changes; the tiles
+// visited, their order and all arithmetic are those of the contiguous form.
+// Causal 16-bit forms only, without pairing, fused RoPE, document mask or the
+// o32 merge (a template argument: the other forms' code does not change).
 #include <cstdlib>
+#include <stdexcept>
 
 #include "fa_common.h"
 #include "kernels.h"
@@ -55,13 +65,15 @@ typedef __attribute__((ext_vector_type(4))) float f4;
 // LDS at the end.  For grids of at most one 4-wave block per CU (Llama-2-70B's
 // 8 heads per TP-8 rank: 256 causal blocks of 1..32 key tiles), where the
 // heaviest block sets the kernel time and one wave per SIMD hides no latency.
-template <typename T, int HD, bool CAUSAL, int WAVES, bool KV2 = false>
+template <typename T, int HD, bool CAUSAL, int WAVES, bool KV2 = false, bool PAGED = false>
 __global__ __launch_bounds__(WAVES * 64, 8 / WAVES) void fa_fwd_k(const AttnParams p) {
   typedef typename MT<T>::x8 x8;
   typedef typename MT<T>::x4 x4;
   static_assert(!KV2 || WAVES == 8, "KV2: two 4-wave halves");
+  static_assert(!PAGED || CAUSAL, "paged keys: causal forms only");
   constexpr int RW = KV2 ? 4 : WAVES;  // waves holding distinct query rows
   constexpr int BMW = RW * 32, KT = 64;
+  static_assert(KV_PAGE % KT == 0, "a key tile must not straddle a page");
   constexpr int KS = HD / 16, DT = HD / 32;
   constexpr int ROWB = HD * 2, RG = 8 * ROWB, PIECES = KT * ROWB / 1024, PPW = PIECES / WAVES;
   constexpr int TB = KT * ROWB;  // bytes of one K (or V) tile
@@ -87,8 +99,8 @@ __global__ __launch_bounds__(WAVES * 64, 8 / WAVES) void fa_fwd_k(const AttnPara
   const int off = p.coff;
 
   const T* Q = (const T*)p.q + (int64_t)b * p.q_sb + (int64_t)g * p.q_sg + (int64_t)(head % r) * p.q_sh;
-  const T* K = (const T*)p.k + (int64_t)b * p.k_sb + (int64_t)g * p.k_sg;
-  const T* V = (const T*)p.v + (int64_t)b * p.v_sb + (int64_t)g * p.v_sg;
+  const T* K = (const T*)p.k + (PAGED ? 0 : (int64_t)b * p.k_sb) + (int64_t)g * p.k_sg;
+  const T* V = (const T*)p.v + (PAGED ? 0 : (int64_t)b * p.v_sb) + (int64_t)g * p.v_sg;
 
   const int m0 = mb * BMW + rw * 32;
   const int qrow = m0 + c;
@@ -143,11 +155,21 @@ __global__ __launch_bounds__(WAVES * 64, 8 / WAVES) void fa_fwd_k(const AttnPara
   }
   auto prefetch = [&](int t, int slot, int g) {
     char* kl = lds + (g * NB + slot) * 2 * TB;
+    int prow = 0;  // PAGED: the first pool row of the tile's page (t * KT < sk <= pt_ld * KV_PAGE)
+    if constexpr (PAGED) {
+      // nothing writes the table while the kernel runs: read through the constant
+      // address space, so that the uniform load is a scalar one (lgkmcnt: the
+      // counted vmcnt of the DMA ring is not disturbed)
+      typedef const __attribute__((address_space(4))) int* ctab;
+      const int pg = ((ctab)p.page_table)[(int64_t)b * p.pt_ld + t * KT / KV_PAGE];
+      prow = min(max(pg, 0), p.n_pages - 1) * KV_PAGE;
+    }
 #pragma unroll
     for (int i = 0; i < PPW; ++i) {
       const int pc = wave * PPW + i;
       int kr = t * KT + srow[i];
       kr = kr < p.sk ? kr : p.sk - 1;
+      if constexpr (PAGED) kr = prow + kr % KV_PAGE;  // the clamped key lies in the tile's page
       __builtin_amdgcn_global_load_lds((const void*)(K + (int64_t)kr * p.k_ss + schunk[i] * 8),
                                        (__attribute__((address_space(3))) void*)(kl + pc * 1024),
                                        16, 0, 0);
@@ -434,6 +456,11 @@ void launch_fwd(const AttnParams& p0, hipStream_t s) {
   const int bmw = 32 * (KV2 ? 4 : WAVES);
   dim3 grid(((p0.sq + bmw - 1) / bmw) * p0.nq * p0.b);
   AttnParams p = p0;
+  if (p.page_table) {  // paged keys: heavy-first order, never paired
+    p.pair_ncu = 0;
+    hipLaunchKernelGGL((fa_fwd_k<T, HD, true, WAVES, KV2, true>), grid, dim3(64 * WAVES), 0, s, p);
+    return;
+  }
   p.pair_ncu = KV2 ? 0 : fa_pair_ncu(p.causal, grid.x, WAVES, HD);
   if (p.causal)
     hipLaunchKernelGGL((fa_fwd_k<T, HD, true, WAVES, KV2>), grid, dim3(64 * WAVES), 0, s, p);
@@ -511,13 +538,22 @@ bool flash_attn_kv2(int b, int sq, int nq, int hd) {
   return fa_kv2_on() && hd == 128 && ncu > 0 && blocks4 <= ncu;
 }
 
-void flash_attn_fwd(const AttnParams& p, int dt, hipStream_t s) {
-  if (flash_attn_kv2(p.b, p.sq, p.nq, p.hd)) {
+void flash_attn_fwd(const AttnParams& p, int dt, hipStream_t s, int waves, int kv2) {
+  if (p.page_table) {
+    if (!p.causal || p.rope_cos || p.doc_start || p.o32)
+      throw std::runtime_error("flash_attn_fwd: a page_table needs the plain causal forward (no "
+                               "fused rope, document mask or o32 merge)");
+    if (p.pt_ld < 1 || p.n_pages < 1 || p.sk > (int64_t)p.pt_ld * KV_PAGE)
+      throw std::runtime_error("flash_attn_fwd: sk exceeds the page_table's pages per row");
+  }
+  if (kv2 > 0 && p.hd != 128) throw std::runtime_error("flash_attn_fwd: kv2 needs head_dim 128");
+  // a forced 4 / 8 waves means that form, not the split-key one
+  if (kv2 < 0 ? (waves == 0 && flash_attn_kv2(p.b, p.sq, p.nq, p.hd)) : kv2 > 0) {
     if (dt == DT_BF16) fa::launch_fwd<bf16, 128, 8, true>(p, s);
     else fa::launch_fwd<fp16, 128, 8, true>(p, s);
     return;
   }
-  const bool w4 = flash_attn_waves(p.b, p.sq, p.nq, p.hd) == 4;
+  const bool w4 = (waves == 4 || waves == 8 ? waves : flash_attn_waves(p.b, p.sq, p.nq, p.hd)) == 4;
   if (dt == DT_BF16) {
     if (p.hd == 128) w4 ? fa::launch_fwd<bf16, 128, 4>(p, s) : fa::launch_fwd<bf16, 128, 8>(p, s);
     else w4 ? fa::launch_fwd<bf16, 64, 4>(p, s) : fa::launch_fwd<bf16, 64, 8>(p, s);

@@ -155,6 +155,15 @@ struct AttnParams {
   // dQ kernels start each query block at its first row's bound, the dK/dV
   // kernel ends each key block at the last query that still sees it.
   int window;
+  // Forward only, paged keys (nullptr: none), as DecodeParams: device int32
+  // [>= b][pt_ld]; k / v are then a pool of n_pages pages of KV_PAGE rows (row
+  // stride k_ss / v_ss; k_sb / v_sb unused) and key i of batch row b is pool
+  // row page_table[b * pt_ld + i / KV_PAGE] * KV_PAGE + i % KV_PAGE (entries
+  // clamped to [0, n_pages)); sq, sk, coff, window and all masking stay
+  // logical.  Causal only; not combined with pairing, fused RoPE, the document
+  // mask or the o32 merge (the launcher refuses).
+  const int* page_table;
+  int pt_ld, n_pages;
 };
 // pair_ncu for a causal grid of `grid` blocks of `waves` waves (0: no pairing);
 // fa_set_pairing(false) turns it off (tests: bitwise equal outputs either way)
@@ -192,7 +201,10 @@ inline int flash_attn_kv_split(int b, int sk, int nq, int nkv) {
 // 8-wave grid would give fewer than two blocks per CU (few heads per TP rank):
 // profiles/r2c_fa_waves_ab.txt.  EMA_FA_WAVES=4|8 overrides.
 int flash_attn_waves(int b, int sq, int nq, int hd);
-void flash_attn_fwd(const AttnParams& p, int dt, hipStream_t s);
+// waves: 0 picks as flash_attn_waves / flash_attn_kv2 do, 4 or 8 forces that
+// form; kv2: -1 automatic, 0 / 1 forces the split-key form off / on (head_dim
+// 128 only).  The choice never depends on p.page_table.
+void flash_attn_fwd(const AttnParams& p, int dt, hipStream_t s, int waves = 0, int kv2 = -1);
 
 // ---- flash_decode.hip: one query token per (batch, head) against a KV cache ----
 // Keys per page of a paged KV cache (inference/paged.py holds the same value):

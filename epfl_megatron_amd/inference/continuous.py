@@ -40,6 +40,24 @@ cannot land in a page that has gone to another row.  ``ContinuousBatcher``
 reserves all of a request's pages at admission from a ``PagePool`` and makes the
 request wait, in order, while the pool is short.
 
+Chunked prefill (``ContinuousBatcher(prefill_chunk=c)``): a prompt is prefilled
+in pieces that end at the multiples of ``c``, back to back, each a ``b = 1``
+call at ``sequence_len_offset`` = the piece's first position; on a paged cache
+``ip.continue_prefill`` is set around the calls and a piece attends over the
+earlier ones through the page table.  Decode replays do not run between the
+pieces of one prompt.
+
+Prefix sharing (``prefix_cache=True``, paged only; ``PrefixCache`` in
+``inference/paged.py``): at admission the prompt's leading full pages are looked
+up in the cache; the row's table starts with the pages found, only the others
+are allocated, and the prefill starts behind them.  After the prefill the row's
+own full prompt pages are registered for later requests.  Shared pages are
+never written: only full prompt pages are shared, the prefill writes at
+positions past the shared pages and the decoder at positions ``>= len(prompt)``.
+A finished row is released first (its later K / V writes go to the null page);
+then its private pages return to the pool and its cached pages lose a reader,
+staying cached until an admission that finds the pool short evicts them.
+
 The reference has no in-flight batching (``megatron/text_generation/
 generation.py`` runs a fixed batch to its longest member); this is an
 MI355X-side addition.
@@ -50,7 +68,7 @@ import torch
 
 from ..parallel import state
 from .hip_graph import broadcast_seed_offset
-from .paged import KV_PAGE, PagePool, pages_for, physical_slots
+from .paged import KV_PAGE, PagePool, PrefixCache, pages_for, physical_slots
 
 _TOO_SHORT = "KV cache too short for max_new_tokens"
 
@@ -429,14 +447,26 @@ class ContinuousBatcher:
     ``decoder``: a ``RaggedSamplingDecoder`` (configured) to sample instead of
     the greedy decoder built by default.  The stop token belongs to the
     decoder: ``stop_id`` here is handed to the decoder this class builds, and
-    with ``decoder=`` it must be left out or agree with the decoder's."""
+    with ``decoder=`` it must be left out or agree with the decoder's.
+
+    ``prefill_chunk``: an integer ``>= 2`` prefills a prompt in pieces that
+    end at the multiples of it (a piece of one token is merged into its
+    neighbour); None: one call per prompt.  ``prefix_cache=True`` (paged cache
+    only) shares the full prompt pages of earlier requests; ``prefix_log``
+    records ``(request id, pages matched)`` per admission, ``prefix_hit_pages``
+    their sum, ``prefilled_tokens`` the tokens the prefills ran and
+    ``evictions`` the cached pages freed for an admission."""
 
     def __init__(self, model, ip, batch, capacity, poll_every=4, max_new_tokens=None, stop_id=None,
-                 decoder=None, capture=None):
+                 decoder=None, capture=None, prefill_chunk=None, prefix_cache=False):
         if capacity > ip.max_sequence_len or batch > ip.max_batch_size:
             raise ValueError("batch / capacity exceed the inference params' cache")
         if poll_every < 1:
             raise ValueError("poll_every must be >= 1")
+        if prefill_chunk is not None and int(prefill_chunk) < 2:
+            raise ValueError("prefill_chunk must be >= 2 (None: the whole prompt in one call)")
+        if prefix_cache and getattr(ip, "page_table", None) is None:
+            raise ValueError("prefix_cache needs a paged KV cache (InferenceParams(kv_pages=...))")
         self.model, self.ip, self.batch, self.capacity = model, ip, batch, capacity
         self.poll_every = poll_every
         if decoder is None:
@@ -459,6 +489,13 @@ class ContinuousBatcher:
         self._idle_since = list(range(batch))  # idle rows are offered the queue oldest first
         self._idle_tick = batch
         self.waits = 0          # admissions that found the pool short
+        self.prefill_chunk = None if prefill_chunk is None else int(prefill_chunk)
+        self.cache = PrefixCache(self.pool) if prefix_cache else None
+        self.row_cached = [None] * batch  # cache entries each busy row holds a reference to
+        self.prefix_log = []    # (request id, pages matched) of every admission
+        self.prefix_hit_pages = 0
+        self.prefilled_tokens = 0
+        self.evictions = 0
 
     def submit(self, prompt_tokens, max_new_tokens):
         """Queue a request; returns its id (= its index in ``run()``'s result)."""
@@ -480,23 +517,49 @@ class ContinuousBatcher:
         self.queue.append(len(self.requests) - 1)
         return len(self.requests) - 1
 
-    def _prefill(self, row, prompt):
-        """Eager ``b = 1`` prefill of ``prompt`` into cache column ``row``; the
-        device slot tensors are hidden so that no layer takes the graph
-        branch, and the host offsets are restored for the decode step (whose
-        graph branch reads neither)."""
+    def _pieces(self, s0, n):
+        """The prefill of positions ``[s0, n)`` as (first, one past the last)
+        pieces: cut at the multiples of ``prefill_chunk``, a piece of one token
+        (which would take the decode step's branch) merged into a neighbour."""
+        if self.prefill_chunk is None:
+            return [(s0, n)]
+        c = self.prefill_chunk
+        cuts = [s0]
+        while cuts[-1] < n:
+            cuts.append(min(n, (cuts[-1] // c + 1) * c))
+        i = 1
+        while i < len(cuts) and len(cuts) > 2:
+            if cuts[i] - cuts[i - 1] == 1:
+                del cuts[i if i < len(cuts) - 1 else i - 1]
+            else:
+                i += 1
+        return list(zip(cuts[:-1], cuts[1:]))
+
+    def _prefill(self, row, prompt, s0=0):
+        """Eager ``b = 1`` prefill of ``prompt`` from position ``s0`` (the keys
+        before it are in the row's shared pages) into cache column ``row``, in
+        the pieces of ``_pieces``; the device slot tensors are hidden so that
+        no layer takes the graph branch, and the host offsets are restored for
+        the decode step (whose graph branch reads neither)."""
         ip, dev = self.ip, self.dec.tokens.device
-        saved = (ip.device_offset, ip.device_kv_len, ip.sequence_len_offset, ip.batch_size_offset)
+        saved = (ip.device_offset, ip.device_kv_len, ip.sequence_len_offset, ip.batch_size_offset,
+                 ip.continue_prefill)
         ip.device_offset = ip.device_kv_len = None
-        ip.sequence_len_offset, ip.batch_size_offset = 0, row
+        ip.batch_size_offset = row
         try:
             n = prompt.numel()
-            pos = torch.arange(n, device=dev)[None]
-            with torch.no_grad():
-                logits = self.model(prompt.to(dev)[None], pos, None, inference_params=ip)
+            tokens = prompt.to(dev)[None]
+            for a, b in self._pieces(s0, n):
+                ip.sequence_len_offset = a
+                ip.continue_prefill = self.paged and a > 0
+                pos = torch.arange(a, b, device=dev)[None]
+                with torch.no_grad():
+                    logits = self.model(tokens[:, a:b], pos, None, inference_params=ip)
+            self.prefilled_tokens += n - s0
             return self._first(logits[:, -1])
         finally:
-            ip.device_offset, ip.device_kv_len, ip.sequence_len_offset, ip.batch_size_offset = saved
+            (ip.device_offset, ip.device_kv_len, ip.sequence_len_offset, ip.batch_size_offset,
+             ip.continue_prefill) = saved
 
     def _first(self, last):
         if self.dec.sample and self.dec.settings["top_k"] != 1:
@@ -512,42 +575,64 @@ class ContinuousBatcher:
         while self.queue:
             rid = self.queue[0]
             prompt, max_new = self.requests[rid]
-            pages = None
+            pages, chain = None, []
             if self.paged:
-                pages = self.pool.alloc(pages_for(prompt.numel() + max_new))
+                need = pages_for(prompt.numel() + max_new)
+                if self.cache is not None:
+                    # the shared pages are held before anything is evicted for the rest
+                    chain = self.cache.match(prompt)
+                    self.cache.acquire(chain)
+                    need -= len(chain)
+                    if need > self.pool.available:
+                        self.evictions += len(self.cache.evict(need - self.pool.available))
+                pages = self.pool.alloc(need)
                 if pages is None:
+                    if self.cache is not None:
+                        self.cache.release(chain)  # it waits without a reference
                     self.waits += 1
                     break
-                self.page_log.append((rid, row, list(pages)))
+                table = [e.page for e in chain] + pages
+                self.page_log.append((rid, row, list(table)))
                 # the table row before the eager prefill, which scatters by it
-                self.dec.write_table(row, pages, prompt.numel() + max_new)
+                self.dec.write_table(row, table, prompt.numel() + max_new)
             self.queue.popleft()
-            first = self._prefill(row, prompt)
+            first = self._prefill(row, prompt, len(chain) * KV_PAGE)
+            if self.cache is not None:
+                self.prefix_log.append((rid, len(chain)))
+                self.prefix_hit_pages += len(chain)
+                # the row's own full prompt pages now belong to the cache
+                chain = chain + self.cache.insert(prompt, table, len(chain))
+                cached = {e.page for e in chain}
+                pages = [p for p in pages if p not in cached]
             if max_new == 1 or (self.dec.stop_id >= 0 and first == self.dec.stop_id):
                 self.results[rid] = [first]  # done on its first token
                 if self.paged:
-                    self._give_back(row, pages)
+                    self._give_back(row, pages, chain)
                 continue
             self.dec.prime(row, first, prompt.numel(), max_new - 1)
             self.primed.append((row, prompt.numel(), max_new - 1))
             self.rows[row] = (rid, first)
             self.row_pages[row] = pages
+            self.row_cached[row] = chain
             return
         self.rows[row] = None
 
-    def _give_back(self, row, pages):
+    def _give_back(self, row, pages, cached=()):
         """The order that keeps a parked row from corrupting its successor:
         ``release`` is enqueued first (the row's later K / V writes go to the
-        null page), then the pages return to the free list."""
+        null page), then the row's private pages return to the free list and
+        its cached pages lose a reader."""
         self.dec.release(row)
         self.pool.free(pages)
+        if cached:
+            self.cache.release(cached)
 
     def _collect(self, row, hist_idx):
         rid, first = self.rows[row]
         self.results[rid] = [first] + self.dec.history[row, :hist_idx[row]].tolist()
         if self.paged:
-            self._give_back(row, self.row_pages[row])
-            self.row_pages[row] = None
+            self._give_back(row, self.row_pages[row], self.row_cached[row] or ())
+            self.row_pages[row] = self.row_cached[row] = None
             self._idle_since[row], self._idle_tick = self._idle_tick, self._idle_tick + 1
         self.rows[row] = None
 

@@ -40,6 +40,10 @@ class InferenceParams:
         self.max_batch_size = max_batch_size
         self.sequence_len_offset = 0
         self.batch_size_offset = 0
+        # paged cache only (host flag): a b = 1 prefill at sequence_len_offset
+        # > 0 continues row batch_size_offset over the keys its table already
+        # names (a shared prefix, an earlier chunk); clear, it raises
+        self.continue_prefill = False
         self.key_value_memory_dict = {}
         # hipGraph decode (inference/hip_graph.py): the cache slot of the new
         # token (int64 [1]) and the valid key count (int32 [1]) on the device;

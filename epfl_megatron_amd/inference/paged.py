@@ -16,9 +16,22 @@ kernel (4 waves x 64 keys) and a multiple of the smaller ones, so that no chunk
 straddles a page and the indirection is one uniform table load per workgroup
 (``csrc/flash_decode.hip``; ``csrc/kernels.h`` holds the same constant).
 
-Out of scope here: prefix sharing and copy-on-write, growing a row page by
-page and preemption (a request's pages are all reserved at admission), paged
-lockstep decoders and beam search, a configurable page size, a server flag.
+Prefix sharing (``PrefixCache``): a full page of prompt tokens whose K / V a
+prefill has written can serve every later prompt that starts with the same
+tokens.  The cache is a host-side index over such pages, a trie whose edges are
+the exact 256 token ids of a page, with a reference count per page (the rows
+reading it now).  A page the cache holds is simply "out" for the ``PagePool``;
+``evict`` hands unreferenced leaves back, least recently used first.  A row that
+shares ``m`` pages starts its prefill at position ``m * KV_PAGE`` and attends
+over the shared keys through its table (the paged forms of the forward
+attention kernel, ``ops.attention.flash_attn_paged``).  Shared pages are never
+written: only full prompt pages are shared, a continued prefill writes at
+positions ``>= m * KV_PAGE`` and the decoder at positions ``>= len(prompt)``.
+
+Out of scope here: copy-on-write and sharing of partial pages, sharing
+generated tokens, growing a row page by page and preemption (a request's pages
+are all reserved at admission), paged lockstep decoders and beam search, a
+configurable page size, a server flag.
 """
 import torch
 
@@ -88,3 +101,125 @@ class PagePool:
             self._out.remove(p)
             self._free.append(p)
         self._free.sort(reverse=True)
+
+
+class _PrefixEntry:
+    """One cached page: a full page of prompt tokens below ``parent``."""
+    __slots__ = ("parent", "key", "page", "refs", "tick", "children")
+
+    def __init__(self, parent, key, page, tick):
+        self.parent, self.key, self.page = parent, key, page
+        self.refs, self.tick, self.children = 0, tick, 0
+
+
+def _page_bytes(prompt, i):
+    return prompt[i * KV_PAGE:(i + 1) * KV_PAGE].numpy().tobytes()
+
+
+def _token_ids(prompt):
+    return torch.as_tensor(prompt, dtype=torch.long).view(-1).cpu()
+
+
+class PrefixCache:
+    """Host index of the full prompt pages whose K / V are in the pool, for
+    prefix sharing.  An entry's key is ``(parent entry, the bytes of the
+    page's KV_PAGE token ids)``, exact (the root's parent is None), its value
+    the page id; it counts the rows reading it (``refs``) and remembers when
+    it was last acquired or released (``tick``).  The cache owns its pages:
+    they stay allocated in ``pool`` until ``evict`` / ``clear`` frees them."""
+
+    def __init__(self, pool):
+        self.pool = pool
+        self._index = {}
+        self._tick = 0
+
+    def __len__(self):
+        return len(self._index)
+
+    def pages(self):
+        """The page ids the cache holds."""
+        return sorted(e.page for e in self._index.values())
+
+    def _touch(self, e):
+        self._tick += 1
+        e.tick = self._tick
+
+    def match(self, prompt):
+        """The longest chain of cached entries for the leading full pages of
+        ``prompt``, at most ``(len(prompt) - 2) // KV_PAGE`` of them: at least
+        two tokens stay to be prefilled (a one-token prefill would take the
+        decode step's branch).  Moves no reference count."""
+        prompt = _token_ids(prompt)
+        chain, parent = [], None
+        for i in range(max(0, (prompt.numel() - 2) // KV_PAGE)):
+            e = self._index.get((parent, _page_bytes(prompt, i)))
+            if e is None:
+                break
+            chain.append(e)
+            parent = e
+        return chain
+
+    def acquire(self, chain):
+        """A row starts reading the chain's pages."""
+        for e in chain:
+            e.refs += 1
+            self._touch(e)
+
+    def release(self, chain):
+        """A row stops reading the chain's pages."""
+        for e in chain:
+            if e.refs < 1:
+                raise ValueError(f"page {e.page} is released more often than acquired")
+        for e in chain:
+            e.refs -= 1
+            self._touch(e)
+
+    def insert(self, prompt, pages, n_matched):
+        """After the prefill of ``prompt`` into the row whose table lists
+        ``pages`` (the ``n_matched`` acquired pages of ``match`` first):
+        register the row's further full prompt pages, ``i >= n_matched`` with
+        ``(i + 1) * KV_PAGE <= len(prompt)``.  Returns the new entries; the row
+        holds a reference to each and the cache owns their pages from now on.
+        Where an identical entry exists already the row keeps its page private
+        (and the walk goes on below the existing entry)."""
+        prompt = _token_ids(prompt)
+        parent = None
+        for i in range(n_matched):
+            parent = self._index[(parent, _page_bytes(prompt, i))]
+            if parent.page != pages[i]:
+                raise ValueError(f"page {pages[i]} is not the cached page of the prompt's page {i}")
+        added = []
+        for i in range(n_matched, min(prompt.numel() // KV_PAGE, len(pages))):
+            key = (parent, _page_bytes(prompt, i))
+            e = self._index.get(key)
+            if e is None:
+                self._tick += 1
+                e = self._index[key] = _PrefixEntry(parent, key, int(pages[i]), self._tick)
+                e.refs = 1
+                if parent is not None:
+                    parent.children += 1
+                added.append(e)
+            parent = e
+        return added
+
+    def evict(self, n):
+        """Free up to ``n`` pages to the pool: entries nobody reads and no
+        cached page continues, least recently used first (a parent becomes
+        eligible once its last child has gone).  Returns the pages freed."""
+        freed = []
+        while len(freed) < n:
+            idle = [e for e in self._index.values() if e.refs == 0 and e.children == 0]
+            if not idle:
+                break
+            for e in sorted(idle, key=lambda e: e.tick)[:n - len(freed)]:
+                del self._index[e.key]
+                if e.parent is not None:
+                    e.parent.children -= 1
+                freed.append(e.page)
+        if freed:
+            self.pool.free(freed)
+        return freed
+
+    def clear(self):
+        """Evict everything unreferenced."""
+        return self.evict(len(self._index))

@@ -35,7 +35,8 @@ from ..ops.norms import RMSNorm, MixedFusedLayerNorm, _param_sync, rms_norm
 from ..ops.rope import rope_table, apply_rope_ref, rope_qkv_inplace, rope_qkv
 from ..ops._ext import use_native, ext
 from ..parallel.context import chunk_position_ids, ring_attention
-from ..ops.attention import flash_attn_qkvpacked, flash_attn_func, flash_decode_cached
+from ..ops.attention import (flash_attn_qkvpacked, flash_attn_func, flash_attn_paged,
+                             flash_decode_cached)
 from ..ops.activations import glu, bias_gelu, gelu
 from ..ops import decode_pack, fp8_kv, fp8_weights, mxfp4_weights
 from ..ops.softmax import FusedScaleMaskSoftmax
@@ -364,8 +365,14 @@ class ParallelAttention(MegatronModule):
         ``ip.device_offset[m]`` (kept physical by the ragged decoders) and reads
         through ``ip.page_table``; the whole-prompt prefill of one row scatters
         its rows to the pool by the row's table, on the device, and attends
-        over the fresh K and V.  Nothing else is supported."""
-        from ..inference.paged import KV_PAGE, physical_slots
+        over the fresh K and V.  With ``ip.continue_prefill`` set, a prefill at
+        ``sequence_len_offset = s0 > 0`` continues the row: its ``sq`` rows go
+        to the pool rows of the positions ``s0 .. s0 + sq - 1`` and the queries
+        attend over the row's ``s0 + sq`` keys through the table
+        (``flash_attn_paged``); the caller vouches that the table covers them
+        and that the first ``s0`` are valid (a shared prefix, an earlier
+        chunk).  Nothing else is supported."""
+        from ..inference.paged import KV_PAGE, gather_rows, physical_slots
         s0, b0 = ip.sequence_len_offset, ip.batch_size_offset
         sq, b = q.shape[:2]
         fp8 = kmem.dtype == torch.uint8
@@ -398,7 +405,7 @@ class ParallelAttention(MegatronModule):
         why = None
         if sq == 1:
             why = "a decode step without device slots (the eager KV-cached loop)"
-        elif s0 > 0:
+        elif s0 > 0 and not getattr(ip, "continue_prefill", False):
             why = "a prefill that continues a cached sequence (sequence_len_offset > 0)"
         elif b > 1:
             why = "a prefill of more than one row"
@@ -411,20 +418,34 @@ class ParallelAttention(MegatronModule):
         # the prompt's rows go to the pool rows its table names: device-side indices
         # (computed by the first layer of a prefill and shared by the others: the
         # table's version counter moves with every write to it)
-        key = (b0, sq, id(ip.page_table), ip.page_table._version)
+        key = (b0, s0, sq, id(ip.page_table), ip.page_table._version)
         if getattr(ip, "_prefill_slots", (None,))[0] != key:
-            ip._prefill_slots = (key, physical_slots(table[0], torch.arange(sq, device=k.device)))
+            ip._prefill_slots = (key, physical_slots(table[0],
+                                                     torch.arange(s0, s0 + sq, device=k.device)))
         idx = ip._prefill_slots[1]
         if fp8 and fp8_kv.store_native_ok(k) and fp8_kv.store_native_ok(v):
-            for p0 in range(0, sq, KV_PAGE):  # a page's rows are consecutive in the pool
-                fp8_kv.store(k[p0:p0 + KV_PAGE], v[p0:p0 + KV_PAGE], kmem, vmem, sc,
-                             slot_t=idx[p0:p0 + 1])
+            p0 = 0
+            while p0 < sq:  # a page's rows are consecutive in the pool: cut at page edges
+                p1 = min(sq, ((s0 + p0) // KV_PAGE + 1) * KV_PAGE - s0)
+                fp8_kv.store(k[p0:p1], v[p0:p1], kmem, vmem, sc, slot_t=idx[p0:p0 + 1])
+                p0 = p1
         elif fp8:
             kmem.index_copy_(0, idx, fp8_kv.quantize(k, sc[0]))
             vmem.index_copy_(0, idx, fp8_kv.quantize(v, sc[1]))
         else:
             kmem.index_copy_(0, idx, k)
             vmem.index_copy_(0, idx, v)
+        if s0 > 0:  # continued: the first s0 keys are in the pages only
+            if self.use_flash_attn:
+                o = flash_attn_paged(q.transpose(0, 1), kmem.transpose(0, 1), vmem.transpose(0, 1),
+                                     table, s0 + sq, window=self._window(s0 + sq), kv_scale=sc)
+                return o.transpose(0, 1).reshape(sq, b, -1)
+            keys, vals = (gather_rows(m, table[0], s0 + sq) for m in (kmem, vmem))
+            if fp8:
+                keys = fp8_kv.dequantize(keys, sc[0], q.dtype)
+                vals = fp8_kv.dequantize(vals, sc[1], q.dtype)
+            return self.core_attention(q, self._expand_kv(keys), self._expand_kv(vals),
+                                       attention_mask)
         if self.use_flash_attn:
             o = flash_attn_func(q.transpose(0, 1), k.transpose(0, 1), v.transpose(0, 1),
                                 causal=True, window=self._window(sq))

@@ -238,6 +238,56 @@ def flash_decode_cached(q, k, v, kv_len, softmax_scale=None, window=0, kv_scale=
     return _flash_decode(q, k, v, scale, kv_len, window, kv_scale)
 
 
+def flash_attn_paged(q, k_pool, v_pool, page_table, sk, softmax_scale=None, window=0,
+                     kv_scale=None, waves=0, kv2=-1):
+    """A block of queries over keys that live in pages (the continued prefill
+    of a paged KV cache, ``inference/paged.py``).  ``q [b, sq, nq, d]`` holds
+    the last ``sq`` of ``sk`` logical positions (causal, bottom-right aligned),
+    the pools are ``[1, n_pages * KV_PAGE, nkv, d]`` and key ``j`` of row ``i``
+    is pool row ``page_table[i, j // KV_PAGE] * KV_PAGE + j % KV_PAGE``
+    (``page_table`` int32 ``[>= b, pages_per_row]``).  No autograd.
+
+    Native 16-bit pools go to the paged forms of the forward kernel
+    (``csrc/flash_attn_fwd.hip``), which read the pages in place.  Everything
+    else (CPU, fp32, other head dims, FP8 pools: uint8 with ``kv_scale`` fp32
+    ``[2, nkv]``) gathers each row's first ``sk`` keys, dequantises FP8 bytes,
+    and runs the contiguous attention on them.  ``waves`` / ``kv2`` force a
+    kernel form (tests), as the ``flash_attn_fwd`` binding takes them."""
+    from ..inference.paged import KV_PAGE, gather_rows
+    _check_window(window, True)
+    b, sq, nq, d = q.shape
+    sk = int(sk)
+    if not 0 < sq <= sk:
+        raise ValueError(f"flash_attn_paged: q holds the last sq of sk positions (sq {sq}, sk {sk})")
+    if sk > page_table.shape[1] * KV_PAGE:
+        raise ValueError("flash_attn_paged: sk exceeds the page_table's pages per row")
+    fp8 = k_pool.dtype == torch.uint8
+    if fp8 != (kv_scale is not None):
+        raise ValueError("an FP8 (uint8) pool needs its kv_scale tensor" if fp8
+                         else "kv_scale given for a 16-bit pool")
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(d)
+    if not fp8 and use_native(q) and d in (64, 128) and k_pool.dtype == q.dtype:
+        nkv = k_pool.shape[2]
+        r = nq // nkv
+        out = torch.empty(b, sq, nq, d, dtype=q.dtype, device=q.device)
+        lse = torch.empty(b, nq, sq, dtype=torch.float32, device=q.device)
+        ext().flash_attn_fwd(q, k_pool, v_pool, out, lse, b, sq, sk, nq, nkv, d,
+                             list(_bsnd_strides(q, r)), list(_bsnd_strides(k_pool, 1)[:3]),
+                             list(_bsnd_strides(v_pool, 1)[:3]),
+                             [out.stride(0), out.stride(1), out.stride(2)], True, float(scale),
+                             None, None, None, None, window=int(window), page_table=page_table,
+                             waves=int(waves), kv2=int(kv2))
+        return out
+    k = torch.stack([gather_rows(k_pool[0], page_table[i], sk) for i in range(b)])
+    v = torch.stack([gather_rows(v_pool[0], page_table[i], sk) for i in range(b)])
+    if fp8:
+        from . import fp8_kv
+        k = fp8_kv.dequantize(k, kv_scale[0], q.dtype)
+        v = fp8_kv.dequantize(v, kv_scale[1], q.dtype)
+    with torch.no_grad():
+        return flash_attn_func(q, k, v, causal=True, softmax_scale=scale, window=window)
+
+
 class _FlashFn(torch.autograd.Function):
     """Separate q ``[b, sq, nq, d]``, k/v ``[b, sk, nkv, d]``."""
 

@@ -26,6 +26,16 @@ of 256 keys (inference/paged.py); reports how often an admission waited for
 pages and the peak pages in use.  --paged_cost: the same requests, seed and
 batch through the unpaged and the paged batcher in one process, alternating.
 
+--continuous --prefix_share: what prefix sharing buys (ContinuousBatcher(prefix_cache=True),
+inference/paged.py PrefixCache).  A seeded request list with one common system
+prompt of --system_prompt tokens and unique tails (--prompt_range) is served
+by the paged batcher without and with the prefix cache, alternating in one
+process, --reps timed repetitions each; then the same for the list without a
+common prefix (prompts drawn from --no_prefix_range: the host cost of matching
+when nothing matches).  Reports useful tokens/s and the mean time from a
+request's admission to its first token.  The baseline is the paged batcher
+without the cache.
+
 --ragged_cost: what per-row state costs a uniform batch: RaggedGreedyDecoder
 against GraphedGreedyDecoder from the same prefilled cache, --reps repetitions
 each, alternating; the spread of the lockstep decoder's repetitions is the margin.
@@ -35,6 +45,8 @@ Usage: python scripts/serve_bench.py [--batches 1,8,32] [--graph]
        [--continuous [--requests N] [--prompt_range LO,HI] [--gen_range LO,HI]
         [--poll_every 1,4,16] [--kv_pages N] [--capacity C]] [--ragged_cost [--reps 3]]
        [--paged_cost [--reps 3] [--kv_pages N]]
+       [--continuous --prefix_share [--system_prompt 1024] [--prompt_range LO,HI]
+        [--no_prefix_range LO,HI] [--prefill_chunk C] [--reps 3]]
 """
 import argparse
 import json
@@ -89,6 +101,15 @@ def main():
     ap.add_argument("--paged_cost", action="store_true",
                     help="the same requests through the unpaged and the paged ContinuousBatcher, "
                          "alternating, --reps repetitions each")
+    ap.add_argument("--prefix_share", action="store_true",
+                    help="--continuous: the paged batcher with and without prefix_cache on a "
+                         "request list with a common system prompt, and on one without")
+    ap.add_argument("--system_prompt", type=int, default=1024,
+                    help="--prefix_share: tokens of the common prefix")
+    ap.add_argument("--no_prefix_range", default="16,1920",
+                    help="--prefix_share: prompt lengths LO,HI of the list without a common prefix")
+    ap.add_argument("--prefill_chunk", type=int, default=0,
+                    help="--prefix_share: ContinuousBatcher prefill_chunk (0: whole prompts)")
     a = ap.parse_args()
     sampling = a.top_k > 0 or a.top_p > 0.0 or a.temperature != 1.0
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=os.environ.get("MASTER_PORT", "29561"),
@@ -131,6 +152,8 @@ def main():
     m = model[0].eval()
     if a.paged_cost:
         return paged_cost(a, m)
+    if a.continuous and a.prefix_share:
+        return prefix_share(a, m)
     if a.continuous:
         return continuous(a, m, sampling, skw)
     if a.ragged_cost:
@@ -325,6 +348,85 @@ def paged_cost(a, m):
                      admission_waits=cbs["paged"].waits, same_tokens=outs["paged"] == outs["unpaged"])
         print(json.dumps(r), flush=True)
         res.append(r)
+    return res
+
+
+def prefix_share(a, m):
+    """--continuous --prefix_share: the paged ContinuousBatcher without and with
+    the prefix cache, alternating, on a list with a common system prompt and
+    on one without; pages enough that no admission waits."""
+    import torch
+    from epfl_megatron_amd.inference import ContinuousBatcher
+    from epfl_megatron_amd.inference.forward_step import InferenceParams
+    from epfl_megatron_amd.inference.paged import pages_for
+    (tlo, thi), (nlo, nhi), (glo, ghi) = ([int(x) for x in r.split(",")]
+                                          for r in (a.prompt_range, a.no_prefix_range, a.gen_range))
+    poll = int(a.poll_every.split(",")[0])
+    res = []
+    for B in [int(x) for x in a.batches.split(",")]:
+        n = a.requests or 4 * B
+        g = torch.Generator().manual_seed(a.seed)
+        system = torch.randint(0, 32000, (a.system_prompt,), generator=g)
+        tails = torch.randint(tlo, thi + 1, (n,), generator=g).tolist()
+        gens = torch.randint(glo, ghi + 1, (n,), generator=g).tolist()
+        lists = {"common_prefix": [torch.cat([system, torch.randint(0, 32000, (t,), generator=g)])
+                                   for t in tails]}
+        plens = torch.randint(nlo, nhi + 1, (n,), generator=g).tolist()
+        lists["no_prefix"] = [torch.randint(0, 32000, (p,), generator=g) for p in plens]
+        useful = sum(gens)
+        for lname, prompts in lists.items():
+            cap = max(max(p.numel() for p in prompts) + ghi, a.capacity)
+            kvp = B * pages_for(cap) + pages_for(a.system_prompt) + 1
+            cbs, secs, ttft, outs = {}, {}, {}, {}
+            for name in ("baseline", "prefix_cache"):
+                ip = InferenceParams(B, cap, kv_pages=kvp)
+                cb = ContinuousBatcher(m, ip, B, cap, poll_every=poll, max_new_tokens=ghi,
+                                       prefix_cache=name == "prefix_cache",
+                                       prefill_chunk=a.prefill_chunk or None)
+                cb.first_token_s = []
+
+                def timed_prefill(row, prompt, s0=0, cb=cb, prefill=cb._prefill):
+                    # admission to first token: the pages are reserved, the prompt is
+                    # prefilled and the first token is read back (a host sync)
+                    t0 = time.perf_counter()
+                    tok = prefill(row, prompt, s0)
+                    cb.first_token_s.append(time.perf_counter() - t0)
+                    return tok
+                cb._prefill = timed_prefill
+                for p in prompts[:B]:  # warm-up: the capture, the allocator, the prefill kernels
+                    cb.submit(p, 4)
+                cb.run()
+                cbs[name], secs[name], ttft[name] = cb, [], []
+            for rep in range(a.reps):
+                for name, cb in cbs.items():
+                    cb.first_token_s.clear()
+                    for p, gn in zip(prompts, gens):
+                        cb.submit(p, gn)
+                    out, dt = _timed(cb.run)
+                    assert [len(o) for o in out[-n:]] == gens and cb.dec.captures == 1
+                    secs[name].append(round(dt, 4))
+                    ttft[name].append(round(1e3 * sum(cb.first_token_s) / n, 3))
+                    outs[name] = out[-n:]
+            r = {"mode": "prefix_share", "list": lname, "batch": B, "requests": n,
+                 "system_prompt": a.system_prompt if lname == "common_prefix" else 0,
+                 "prompt_tokens": sum(p.numel() for p in prompts), "gen_range": [glo, ghi],
+                 "capacity": cap, "kv_pages": kvp, "poll_every": poll, "useful_tokens": useful,
+                 "prefill_chunk": a.prefill_chunk}
+            for name, cb in cbs.items():
+                r[name + "_seconds"] = secs[name]
+                r[name + "_tokens_per_s"] = [round(useful / t, 1) for t in secs[name]]
+                r[name + "_first_token_ms"] = ttft[name]
+            cb = cbs["prefix_cache"]
+            mean = {k: sum(v) / len(v) for k, v in secs.items()}
+            r.update(baseline_spread_s=round(max(secs["baseline"]) - min(secs["baseline"]), 4),
+                     cache_minus_baseline_s=round(mean["prefix_cache"] - mean["baseline"], 4),
+                     cache_minus_baseline_pct=round(100 * (mean["prefix_cache"] / mean["baseline"] - 1), 2),
+                     prefix_hit_pages=cb.prefix_hit_pages, prefilled_tokens=cb.prefilled_tokens,
+                     baseline_prefilled_tokens=cbs["baseline"].prefilled_tokens,
+                     evictions=cb.evictions, admission_waits=cb.waits,
+                     same_tokens=outs["prefix_cache"] == outs["baseline"])
+            print(json.dumps(r), flush=True)
+            res.append(r)
     return res
 
 
