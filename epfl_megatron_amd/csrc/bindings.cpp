@@ -477,9 +477,11 @@ ema::AttnParams make_attn(const at::Tensor& q, const at::Tensor& k, const at::Te
                           const std::vector<int64_t>& qs, const std::vector<int64_t>& ks,
                           const std::vector<int64_t>& vs, const std::vector<int64_t>& os,
                           bool causal, double scale, bool lse_view = false,
-                          int64_t pool_rows = 0) {
+                          int64_t pool_rows = 0, bool kv8 = false) {
   TORCH_CHECK(qs.size() == 4 && ks.size() == 3 && vs.size() == 3 && os.size() == 3, "bad strides");
-  TORCH_CHECK(q.scalar_type() == k.scalar_type() && q.scalar_type() == v.scalar_type() &&
+  // (kv8: k / v hold e4m3 bytes, uint8, and ks / vs count bytes)
+  const auto kv_t = kv8 ? at::kByte : q.scalar_type();
+  TORCH_CHECK(k.scalar_type() == kv_t && v.scalar_type() == kv_t &&
               q.scalar_type() == out.scalar_type(), "q/k/v/out dtype mismatch");
   TORCH_CHECK(ema::flash_attn_supported((int)hd, dtype_code(q)), "flash attention supports bf16/fp16 "
               "with head_dim 64 or 128 (got ", hd, ")");
@@ -489,8 +491,9 @@ ema::AttnParams make_attn(const at::Tensor& q, const at::Tensor& k, const at::Te
                   (lse_view || lse.is_contiguous()),
               "lse must be fp32 [b, nq, sq]");
   for (int64_t s : qs) TORCH_CHECK(s % 8 == 0, "q strides must keep 16-byte alignment");
-  for (int64_t s : ks) TORCH_CHECK(s % 8 == 0, "k strides must keep 16-byte alignment");
-  for (int64_t s : vs) TORCH_CHECK(s % 8 == 0, "v strides must keep 16-byte alignment");
+  const int64_t kv_al = 16 / (int64_t)k.element_size();
+  for (int64_t s : ks) TORCH_CHECK(s % kv_al == 0, "k strides must keep 16-byte alignment");
+  for (int64_t s : vs) TORCH_CHECK(s % kv_al == 0, "v strides must keep 16-byte alignment");
   for (int64_t s : os) TORCH_CHECK(s % 4 == 0, "o strides must keep 8-byte alignment");
   for (const at::Tensor* t : {&q, &k, &v}) check_vec_aligned(*t, "q/k/v");
   // Every address the kernel can form must lie inside its tensor's storage.
@@ -575,6 +578,8 @@ static void set_window(ema::AttnParams& p, int64_t window) {
   p.window = window >= (int64_t)p.sq + p.coff ? 0 : (int)window;
 }
 
+static const float* kv_scale_ptr(const at::Tensor& sc, int64_t nkv, const at::Tensor& x);
+
 void flash_attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, at::Tensor out,
                     at::Tensor lse, int64_t b, int64_t sq, int64_t sk, int64_t nq, int64_t nkv,
                     int64_t hd, std::vector<int64_t> qs, std::vector<int64_t> ks,
@@ -583,8 +588,25 @@ void flash_attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& 
                     const c10::optional<at::Tensor>& rope_sin,
                     const c10::optional<at::Tensor>& rope_pos,
                     const c10::optional<at::Tensor>& docs, int64_t window,
-                    const c10::optional<at::Tensor>& page_table, int64_t waves, int64_t kv2) {
+                    const c10::optional<at::Tensor>& page_table, int64_t waves, int64_t kv2,
+                    const c10::optional<at::Tensor>& kv_scale) {
   check_gpu(q, "q");
+  // FP8 keys: k / v hold e4m3 bytes (uint8, strides ks / vs in bytes) and
+  // kv_scale is fp32 [2, nkv]; with or without a page_table
+  const bool kv8 = k.scalar_type() == at::kByte;
+  const bool has_sc = kv_scale.has_value() && kv_scale->defined();
+  TORCH_CHECK(kv8 == has_sc, kv8 ? "FP8 (uint8) k / v need their kv_scale tensor"
+                                 : "kv_scale given for 16-bit k / v");
+  if (kv8) {
+    TORCH_CHECK(v.scalar_type() == at::kByte, "FP8 k needs FP8 (uint8) v");
+    TORCH_CHECK(causal, "FP8 (uint8) k / v with kv_scale need causal attention");
+    TORCH_CHECK(!(rope_cos.has_value() && rope_cos->defined()),
+                "rope_cos cannot be combined with FP8 (uint8) k / v and kv_scale");
+    TORCH_CHECK(!(docs.has_value() && docs->defined()),
+                "docs cannot be combined with FP8 (uint8) k / v and kv_scale");
+    TORCH_CHECK(k.is_cuda() && v.is_cuda() && k.device() == q.device() && v.device() == q.device(),
+                "k / v on another device");
+  }
   TORCH_CHECK(waves == 0 || waves == 4 || waves == 8, "waves must be 0 (automatic), 4 or 8");
   TORCH_CHECK(kv2 >= -1 && kv2 <= 1, "kv2 must be -1 (automatic), 0 or 1");
   TORCH_CHECK(kv2 != 1 || (hd == 128 && waves == 0),
@@ -616,11 +638,15 @@ void flash_attn_fwd(const at::Tensor& q, const at::Tensor& k, const at::Tensor& 
                 "k / v on another device");
   }
   auto p = make_attn(q, k, v, out, lse, b, sq, sk, nq, nkv, hd, qs, ks, vs, os, causal, scale, false,
-                     n_pages * ema::KV_PAGE);
+                     n_pages * ema::KV_PAGE, kv8);
   if (paged) {
     p.page_table = page_table->data_ptr<int>();
     p.pt_ld = (int)pt_ld;
     p.n_pages = (int)n_pages;
+  }
+  if (kv8) {
+    p.k_scale = kv_scale_ptr(*kv_scale, nkv, q);
+    p.v_scale = p.k_scale + nkv;
   }
   set_rope(p, rope_cos, rope_sin, rope_pos);
   set_docs(p, docs);
@@ -1595,7 +1621,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("hd"), py::arg("qs"), py::arg("ks"), py::arg("vs"), py::arg("os"),
         py::arg("causal"), py::arg("scale"), py::arg("rope_cos"), py::arg("rope_sin"),
         py::arg("rope_pos"), py::arg("docs"), py::arg("window") = 0,
-        py::arg("page_table") = py::none(), py::arg("waves") = 0, py::arg("kv2") = -1);
+        py::arg("page_table") = py::none(), py::arg("waves") = 0, py::arg("kv2") = -1,
+        py::arg("kv_scale") = py::none());
   m.def("flash_attn_fwd_merge", &flash_attn_fwd_merge, py::arg("q"), py::arg("k"), py::arg("v"),
         py::arg("o32"), py::arg("lse"), py::arg("b"), py::arg("sq"), py::arg("sk"), py::arg("nq"),
         py::arg("nkv"), py::arg("hd"), py::arg("qs"), py::arg("ks"), py::arg("vs"),

@@ -42,10 +42,23 @@
 // KT divides KV_PAGE, so a tile lies in one page: its page is one uniform
 // (scalar) table load per tile and only the DMA's source row changes; the tiles
 // visited, their order and all arithmetic are those of the contiguous form.
-// Causal 16-bit forms only, without pairing, fused RoPE, document mask or the
-// o32 merge (a template argument: the other forms' code does not change).
+// Causal forms only, without pairing, fused RoPE, document mask or the o32
+// merge (a template argument: the other forms' code does not change).
+//
+// FP8 keys (FP8, p.k_scale set: the continued prefill of an FP8 KV cache,
+// ops/fp8_kv.py): k / v are OCP e4m3 bytes (strides in bytes), paged or not.
+// The DMA cannot expand bytes, so a tile is staged through registers: where
+// the 16-bit forms issue the DMA a lane loads 16 B of one key row (16 dims,
+// two of the image's 16-B chunks), and after the tile's MFMAs it expands them
+// to T (v_cvt_pk_f32_fp8 and a pack, exact) and writes the two chunks to their
+// swizzled places (2-slot ring: the slot of the tile before, whose reads the
+// last barrier retired).  The LDS image, every read of it and all arithmetic
+// are the 16-bit form's on the unscaled values; the group's K scale folds into
+// the score scale and its V scale into the final 1 / l (lse does not see it).
+// Causal forms only, with the restrictions of the paged forms.
 #include <cstdlib>
 #include <stdexcept>
+#include <type_traits>
 
 #include "fa_common.h"
 #include "kernels.h"
@@ -65,19 +78,22 @@ typedef __attribute__((ext_vector_type(4))) float f4;
 // LDS at the end.  For grids of at most one 4-wave block per CU (Llama-2-70B's
 // 8 heads per TP-8 rank: 256 causal blocks of 1..32 key tiles), where the
 // heaviest block sets the kernel time and one wave per SIMD hides no latency.
-template <typename T, int HD, bool CAUSAL, int WAVES, bool KV2 = false, bool PAGED = false>
+template <typename T, int HD, bool CAUSAL, int WAVES, bool KV2 = false, bool PAGED = false,
+          bool FP8 = false>
 __global__ __launch_bounds__(WAVES * 64, 8 / WAVES) void fa_fwd_k(const AttnParams p) {
   typedef typename MT<T>::x8 x8;
   typedef typename MT<T>::x4 x4;
   static_assert(!KV2 || WAVES == 8, "KV2: two 4-wave halves");
   static_assert(!PAGED || CAUSAL, "paged keys: causal forms only");
+  static_assert(!FP8 || CAUSAL, "FP8 keys: causal forms only");
+  typedef typename std::conditional<FP8, uint8_t, T>::type TK;  // a stored K / V element
   constexpr int RW = KV2 ? 4 : WAVES;  // waves holding distinct query rows
   constexpr int BMW = RW * 32, KT = 64;
   static_assert(KV_PAGE % KT == 0, "a key tile must not straddle a page");
   constexpr int KS = HD / 16, DT = HD / 32;
   constexpr int ROWB = HD * 2, RG = 8 * ROWB, PIECES = KT * ROWB / 1024, PPW = PIECES / WAVES;
   constexpr int TB = KT * ROWB;  // bytes of one K (or V) tile
-  constexpr int NB = (WAVES == 8 && !KV2) ? 3 : 2;
+  constexpr int NB = (WAVES == 8 && !KV2 && !FP8) ? 3 : 2;
   constexpr int NG = KV2 ? 2 : 1;  // key halves, each with its own ring
   static_assert(PIECES % WAVES == 0, "pieces per wave");
   __shared__ __attribute__((aligned(1024))) char lds[NG * NB * 2 * TB];
@@ -99,8 +115,8 @@ __global__ __launch_bounds__(WAVES * 64, 8 / WAVES) void fa_fwd_k(const AttnPara
   const int off = p.coff;
 
   const T* Q = (const T*)p.q + (int64_t)b * p.q_sb + (int64_t)g * p.q_sg + (int64_t)(head % r) * p.q_sh;
-  const T* K = (const T*)p.k + (PAGED ? 0 : (int64_t)b * p.k_sb) + (int64_t)g * p.k_sg;
-  const T* V = (const T*)p.v + (PAGED ? 0 : (int64_t)b * p.v_sb) + (int64_t)g * p.v_sg;
+  const TK* K = (const TK*)p.k + (PAGED ? 0 : (int64_t)b * p.k_sb) + (int64_t)g * p.k_sg;
+  const TK* V = (const TK*)p.v + (PAGED ? 0 : (int64_t)b * p.v_sb) + (int64_t)g * p.v_sg;
 
   const int m0 = mb * BMW + rw * 32;
   const int qrow = m0 + c;
@@ -123,11 +139,12 @@ __global__ __launch_bounds__(WAVES * 64, 8 / WAVES) void fa_fwd_k(const AttnPara
   // row's bound are masked.  The bound grows with the row, so the wave's last
   // row tells whether a tile needs the mask.  A window alone costs no loads.
   int t0 = 0, wt0 = 0, ds_row = 0, ds_wmax = 0;
-  if (CAUSAL && (p.doc_start || p.window > 0)) {
+  // (FP8 keys: the launcher refuses a document mask, compiled out)
+  if (CAUSAL && ((!FP8 && p.doc_start) || p.window > 0)) {
     const int r0 = mb * BMW < p.sq ? mb * BMW : p.sq - 1;
     const int w0 = m0 < p.sq ? m0 : p.sq - 1, w1 = m0 + 31 < p.sq ? m0 + 31 : p.sq - 1;
     int l0 = 0, lw0 = 0;
-    if (p.doc_start) {
+    if (!FP8 && p.doc_start) {
       const int* D = p.doc_start + (int64_t)b * p.sq;
       l0 = D[r0];
       lw0 = D[w0];
@@ -153,6 +170,17 @@ __global__ __launch_bounds__(WAVES * 64, 8 / WAVES) void fa_fwd_k(const AttnPara
     srow[i] = 8 * (o / RG) + rem2 / 64;
     schunk[i] = 4 * (rem / 512) + (((rem2 % 64) / 16) ^ ((srow[i] >> 2) & 3));
   }
+  // FP8: the tile's K rows then its V rows (2 KT rows of HD bytes) as 16-B
+  // units, HD / 16 to a row, dealt over the block's threads in NU passes of RP
+  // rows: in pass i this thread has bytes 16 uj .. 16 uj + 15 of row i RP + ur.
+  // They land at chunks 2 uj (udst + i RP / 8 RG: the V image follows the K
+  // image, TB = 8 RG) and 2 uj + 1 (that ^ 16) of the slot.
+  typedef __attribute__((ext_vector_type(4))) uint32_t u4;
+  constexpr int NU = FP8 ? HD / (8 * WAVES) : 1, RP = WAVES * 64 * 16 / HD;
+  static_assert(!FP8 || NU * RP == 2 * KT, "staging passes cover K and V");
+  const int ur = tid / (HD / 16), uj = tid % (HD / 16);
+  const int udst = ia_off<HD>(ur, 2 * uj);
+  u4 stg[NG][NU];
   auto prefetch = [&](int t, int slot, int g) {
     char* kl = lds + (g * NB + slot) * 2 * TB;
     int prow = 0;  // PAGED: the first pool row of the tile's page (t * KT < sk <= pt_ld * KV_PAGE)
@@ -163,6 +191,19 @@ __global__ __launch_bounds__(WAVES * 64, 8 / WAVES) void fa_fwd_k(const AttnPara
       typedef const __attribute__((address_space(4))) int* ctab;
       const int pg = ((ctab)p.page_table)[(int64_t)b * p.pt_ld + t * KT / KV_PAGE];
       prow = min(max(pg, 0), p.n_pages - 1) * KV_PAGE;
+    }
+    if constexpr (FP8) {
+#pragma unroll
+      for (int i = 0; i < NU; ++i) {
+        const bool isv = RP > KT ? ur >= KT : i * RP >= KT;  // (RP > KT: one pass, wave-uniform)
+        int kr = t * KT + (i * RP) % KT + (RP > KT ? ur % KT : ur);
+        kr = kr < p.sk ? kr : p.sk - 1;
+        if constexpr (PAGED) kr = prow + kr % KV_PAGE;
+        const uint8_t* src = isv ? (const uint8_t*)V + (int64_t)kr * p.v_ss
+                                 : (const uint8_t*)K + (int64_t)kr * p.k_ss;
+        stg[g][i] = *reinterpret_cast<const u4*>(src + 16 * uj);
+      }
+      return;
     }
 #pragma unroll
     for (int i = 0; i < PPW; ++i) {
@@ -176,6 +217,29 @@ __global__ __launch_bounds__(WAVES * 64, 8 / WAVES) void fa_fwd_k(const AttnPara
       __builtin_amdgcn_global_load_lds((const void*)(V + (int64_t)kr * p.v_ss + schunk[i] * 8),
                                        (__attribute__((address_space(3))) void*)(kl + TB + pc * 1024),
                                        16, 0, 0);
+    }
+  };
+  // FP8: expand the staged bytes of group g's tile into its slot (the compiler
+  // waits on the lane's own staging loads here; the barrier that follows
+  // retires the writes)
+  auto commit = [&](int slot, int g) {
+    if constexpr (FP8) {
+      char* kl = lds + (g * NB + slot) * 2 * TB;
+#pragma unroll
+      for (int i = 0; i < NU; ++i) {
+        x8 c0, c1;
+#pragma unroll
+        for (int w = 0; w < 2; ++w) {
+          const f2 a0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)stg[g][i][w], false);
+          const f2 a1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)stg[g][i][w], true);
+          const f2 b0 = __builtin_amdgcn_cvt_pk_f32_fp8((int)stg[g][i][2 + w], false);
+          const f2 b1 = __builtin_amdgcn_cvt_pk_f32_fp8((int)stg[g][i][2 + w], true);
+          c0[4 * w] = (T)a0[0]; c0[4 * w + 1] = (T)a0[1]; c0[4 * w + 2] = (T)a1[0]; c0[4 * w + 3] = (T)a1[1];
+          c1[4 * w] = (T)b0[0]; c1[4 * w + 1] = (T)b0[1]; c1[4 * w + 2] = (T)b1[0]; c1[4 * w + 3] = (T)b1[1];
+        }
+        *reinterpret_cast<x8*>(kl + udst + i * (RP / 8) * RG) = c0;
+        *reinterpret_cast<x8*>(kl + (udst ^ 16) + i * (RP / 8) * RG) = c1;
+      }
     }
   };
   // this wave's key tiles [gs, ge) over niter barrier-synchronous iterations
@@ -195,7 +259,7 @@ __global__ __launch_bounds__(WAVES * 64, 8 / WAVES) void fa_fwd_k(const AttnPara
   x8 qf[KS];
 #pragma unroll
   for (int kk = 0; kk < KS; ++kk) qf[kk] = ld8(Q + (int64_t)qrow_c * p.q_ss + kk * 16 + 8 * h);
-  if (p.rope_cos) {
+  if (!FP8 && p.rope_cos) {  // (the launcher refuses both with FP8 keys: compiled out there)
     const float *rc, *rs;
     rope_rows<HD>(p, b, qrow_c, rc, rs);
     rope_rows_fwd<T, KS>(qf, rc, rs, h);  // table loads batched (not one round trip per fragment)
@@ -213,7 +277,12 @@ __global__ __launch_bounds__(WAVES * 64, 8 / WAVES) void fa_fwd_k(const AttnPara
 #pragma unroll
     for (int i = 0; i < 16; ++i) o[d][i] = 0.f;
   float m_i = -INFINITY, l_i = 0.f;
-  const float sl2 = p.scale * 1.4426950408889634f;
+  float sl2 = p.scale * 1.4426950408889634f, vsc = 1.f;
+  if constexpr (FP8) {
+    typedef const __attribute__((address_space(4))) float* csc;
+    sl2 = (p.scale * ((csc)p.k_scale)[g]) * 1.4426950408889634f;
+    vsc = ((csc)p.v_scale)[g];
+  }
 
   int rowb[2], trb[2];
 #pragma unroll
@@ -221,6 +290,14 @@ __global__ __launch_bounds__(WAVES * 64, 8 / WAVES) void fa_fwd_k(const AttnPara
     rowb[x] = RG * (c >> 3) + 64 * (c & 7) + 16 * ((2 * x + h) ^ ((c >> 2) & 3));
     trb[x] = RG * x + 64 * (4 * h + tq) + 16 * ((2 * ((lane >> 4) & 1) + (tp >> 1)) ^ ((h + 2 * x) & 3)) +
              8 * (tp & 1);
+  }
+  if constexpr (FP8) {
+    if constexpr (KV2) {
+      if (half > 0) commit(0, 0);
+      if (t0 + half < ntiles) commit(0, 1);
+    } else {
+      if (t0 < ntiles) commit(t0 % NB, 0);
+    }
   }
   __syncthreads();  // vmcnt(0) + barrier: tile 0 (and 1) landed
   if (p.stamps) st1 = fa::wall_stamp();
@@ -348,6 +425,16 @@ __global__ __launch_bounds__(WAVES * 64, 8 / WAVES) void fa_fwd_k(const AttnPara
             o[dc] = MT<T>::mfma(join<T>(vf[sub][sc][dc][0], vf[sub][sc][dc][1]), pf, o[dc]);
         }
     }
+    if constexpr (FP8) {
+      if constexpr (KV2) {
+        if (it + 1 < niter) {
+          commit((it + 1) & 1, 0);
+          if (t0 + half + it + 1 < ntiles) commit((it + 1) & 1, 1);
+        }
+      } else {
+        if (t + 1 < ntiles) commit((t + 1) % NB, 0);
+      }
+    }
     if (NB == 3 && t + 2 < ntiles) {
       // counted: tile t+1 landed, tile t+2's DMA (2 * PPW instructions) may fly on
       asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"i"(2 * PPW) : "memory");
@@ -383,7 +470,7 @@ __global__ __launch_bounds__(WAVES * 64, 8 / WAVES) void fa_fwd_k(const AttnPara
           for (int i = 0; i < 16; ++i) o[d][i] = o[d][i] * aA + ob[((rw * DT + d) * 16 + i) * 64 + lane] * aB;
         m_i = m;
       }
-      if (p.rope_cos && qrow < p.sq) {
+      if (!FP8 && p.rope_cos && qrow < p.sq) {
         T* Qw = const_cast<T*>(Q) + (int64_t)qrow * p.q_ss + 8 * h;
 #pragma unroll
         for (int kk = 0; kk < KS; ++kk) *reinterpret_cast<x8*>(Qw + kk * 16) = qf[kk];
@@ -392,10 +479,11 @@ __global__ __launch_bounds__(WAVES * 64, 8 / WAVES) void fa_fwd_k(const AttnPara
   }
   if (p.stamps) st2 = fa::wall_stamp();
   if ((!KV2 || grp == 0) && qrow < p.sq) {
-    const float inv = l_i > 0.f ? 1.f / l_i : 0.f;
+    float inv = l_i > 0.f ? 1.f / l_i : 0.f;
+    if constexpr (FP8) inv *= vsc;
     const float lse_j = l_i > 0.f ? (m_i + __log2f(l_i)) * 0.6931471805599453f : -INFINITY;
     float* lp = p.lse + (int64_t)b * p.lse_sb + (int64_t)head * p.lse_sh + qrow;
-    if (p.o32) {
+    if (!FP8 && p.o32) {
       // ring-attention step: combine with the running (O, lse) in place
       float w_old = 0.f, w_new = inv, lse_new = lse_j;
       if (p.merge) {
@@ -456,6 +544,14 @@ void launch_fwd(const AttnParams& p0, hipStream_t s) {
   const int bmw = 32 * (KV2 ? 4 : WAVES);
   dim3 grid(((p0.sq + bmw - 1) / bmw) * p0.nq * p0.b);
   AttnParams p = p0;
+  if (p.k_scale) {  // FP8 keys (paged or not): heavy-first order, never paired
+    p.pair_ncu = 0;
+    if (p.page_table)
+      hipLaunchKernelGGL((fa_fwd_k<T, HD, true, WAVES, KV2, true, true>), grid, dim3(64 * WAVES), 0, s, p);
+    else
+      hipLaunchKernelGGL((fa_fwd_k<T, HD, true, WAVES, KV2, false, true>), grid, dim3(64 * WAVES), 0, s, p);
+    return;
+  }
   if (p.page_table) {  // paged keys: heavy-first order, never paired
     p.pair_ncu = 0;
     hipLaunchKernelGGL((fa_fwd_k<T, HD, true, WAVES, KV2, true>), grid, dim3(64 * WAVES), 0, s, p);
@@ -545,6 +641,11 @@ void flash_attn_fwd(const AttnParams& p, int dt, hipStream_t s, int waves, int k
                                "fused rope, document mask or o32 merge)");
     if (p.pt_ld < 1 || p.n_pages < 1 || p.sk > (int64_t)p.pt_ld * KV_PAGE)
       throw std::runtime_error("flash_attn_fwd: sk exceeds the page_table's pages per row");
+  }
+  if (p.k_scale) {
+    if (!p.v_scale || !p.causal || p.rope_cos || p.doc_start || p.o32)
+      throw std::runtime_error("flash_attn_fwd: FP8 k / v need the plain causal forward (no fused "
+                               "rope, document mask or o32 merge)");
   }
   if (kv2 > 0 && p.hd != 128) throw std::runtime_error("flash_attn_fwd: kv2 needs head_dim 128");
   // a forced 4 / 8 waves means that form, not the split-key one

@@ -164,6 +164,14 @@ struct AttnParams {
   // mask or the o32 merge (the launcher refuses).
   const int* page_table;
   int pt_ld, n_pages;
+  // Forward only, FP8 keys (nullptr: none): k / v hold OCP e4m3 bytes (their
+  // strides are then in bytes, rows 16-byte aligned) and k_scale / v_scale are
+  // device fp32 [nkv], as DecodeParams: a stored byte stands for value * scale.
+  // The kernel runs on the unscaled values, folds k_scale[g] into the score
+  // scale and v_scale[g] into the final normalisation.  With or without a
+  // page_table, and under its restrictions.
+  const float* k_scale;
+  const float* v_scale;
 };
 // pair_ncu for a causal grid of `grid` blocks of `waves` waves (0: no pairing);
 // fa_set_pairing(false) turns it off (tests: bitwise equal outputs either way)

@@ -36,7 +36,7 @@ from ..ops.rope import rope_table, apply_rope_ref, rope_qkv_inplace, rope_qkv
 from ..ops._ext import use_native, ext
 from ..parallel.context import chunk_position_ids, ring_attention
 from ..ops.attention import (flash_attn_qkvpacked, flash_attn_func, flash_attn_paged,
-                             flash_decode_cached)
+                             flash_attn_fp8_kv, flash_decode_cached)
 from ..ops.activations import glu, bias_gelu, gelu
 from ..ops import decode_pack, fp8_kv, fp8_weights, mxfp4_weights
 from ..ops.softmax import FusedScaleMaskSoftmax
@@ -466,7 +466,8 @@ class ParallelAttention(MegatronModule):
         """``_inference_forward`` over an FP8 cache: the new rows go through the
         quantising store; the restart prefill attends over its fresh 16-bit K
         and V, a decode step on the native path reads the bytes in the FP8
-        decode kernel, and everything else dequantises the slice it needs."""
+        decode kernel, a continued prefill on it in the FP8 forms of the
+        forward kernel, and everything else dequantises the slice it needs."""
         s0, b0 = ip.sequence_len_offset, ip.batch_size_offset
         sq, b = q.shape[:2]
         sc = self._kv_scales(ip, q.device)
@@ -488,6 +489,13 @@ class ParallelAttention(MegatronModule):
             o = flash_decode_cached(q.transpose(0, 1), kc[:s0 + 1].transpose(0, 1),
                                     vc[:s0 + 1].transpose(0, 1), None,
                                     window=self._window(s0 + 1), kv_scale=sc)
+            return o.transpose(0, 1).reshape(sq, b, -1)
+        if s0 > 0 and native and self.use_flash_attn:
+            # continued prefill: the FP8 forms of the forward kernel read the
+            # stored bytes (the new rows' own included) in place
+            o = flash_attn_fp8_kv(q.transpose(0, 1), kc[:s0 + sq].transpose(0, 1),
+                                  vc[:s0 + sq].transpose(0, 1), sc,
+                                  window=self._window(s0 + sq))
             return o.transpose(0, 1).reshape(sq, b, -1)
         if s0 == 0:
             keys, vals = k, v

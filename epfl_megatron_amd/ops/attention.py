@@ -22,6 +22,7 @@ CPU tensors use an exact fp32 math reference (GPU test oracle and the gloo
 plumbing path).
 """
 import math
+import os
 
 import torch
 
@@ -238,6 +239,71 @@ def flash_decode_cached(q, k, v, kv_len, softmax_scale=None, window=0, kv_scale=
     return _flash_decode(q, k, v, scale, kv_len, window, kv_scale)
 
 
+# Native FP8 prefill (uint8 e4m3 K / V read in place by the FP8 forms of the
+# forward kernel).  EMA_FA_FP8_PREFILL=0 / FP8_PREFILL_NATIVE = False: the
+# fallback that gathers and dequantises into 16-bit tensors first (A/B knob).
+FP8_PREFILL_NATIVE = os.environ.get("EMA_FA_FP8_PREFILL", "1") != "0"
+# calls that took the native FP8 forms / the dequantising fallback (tests)
+fp8_prefill_calls = {"native": 0, "fallback": 0}
+
+
+def _fp8_prefill_native(q, k8, v8, kv_scale):
+    """uint8 K / V of these queries go to the FP8 forms of the forward kernel."""
+    d = q.shape[-1]
+    ok = (FP8_PREFILL_NATIVE and use_native(q) and d in (64, 128)
+          and q.dtype in (torch.bfloat16, torch.float16)
+          and k8.is_cuda and v8.is_cuda and kv_scale.is_cuda)
+    fp8_prefill_calls["native" if ok else "fallback"] += 1
+    return ok
+
+
+def _flash_fwd_fp8(q, k8, v8, kv_scale, sk, scale, window, page_table, waves, kv2):
+    b, sq, nq, d = q.shape
+    nkv = k8.shape[2]
+    r = nq // nkv
+    out = torch.empty(b, sq, nq, d, dtype=q.dtype, device=q.device)
+    lse = torch.empty(b, nq, sq, dtype=torch.float32, device=q.device)
+    ext().flash_attn_fwd(q, k8, v8, out, lse, b, sq, sk, nq, nkv, d,
+                         list(_bsnd_strides(q, r)), list(_bsnd_strides(k8, 1)[:3]),
+                         list(_bsnd_strides(v8, 1)[:3]),
+                         [out.stride(0), out.stride(1), out.stride(2)], True, float(scale),
+                         None, None, None, None, window=int(window), page_table=page_table,
+                         waves=int(waves), kv2=int(kv2), kv_scale=kv_scale)
+    return out
+
+
+def flash_attn_fp8_kv(q, k8, v8, kv_scale, softmax_scale=None, window=0, waves=0, kv2=-1):
+    """A block of queries over the keys of an FP8 cache (the continued prefill
+    of ``--inference_fp8_kv_cache``).  ``q [b, sq, nq, d]`` holds the last
+    ``sq`` of ``sk`` positions (causal, bottom-right aligned); ``k8 / v8 [b, sk,
+    nkv, d]`` are uint8 views of e4m3fn bytes (any strides with ``d``
+    contiguous and 16-byte aligned rows: the cache ``[max_seq, max_batch, nkv,
+    d]`` sliced and transposed) and ``kv_scale`` is fp32 ``[2, nkv]``
+    (``ops/fp8_kv.py``).  No autograd.
+
+    On the GPU (bf16 / fp16 queries, head_dim 64 / 128) the FP8 forms of the
+    forward kernel read the bytes in place; everything else dequantises into
+    ``q``'s dtype and runs the contiguous attention.  ``waves`` / ``kv2`` force
+    a kernel form (tests)."""
+    _check_window(window, True)
+    if k8.dtype != torch.uint8 or v8.dtype != torch.uint8:
+        raise ValueError("flash_attn_fp8_kv: k8 / v8 must be uint8 (e4m3fn bytes)")
+    if kv_scale is None:
+        raise ValueError("flash_attn_fp8_kv: an FP8 (uint8) cache needs its kv_scale tensor")
+    b, sq, nq, d = q.shape
+    sk = k8.shape[1]
+    if not 0 < sq <= sk:
+        raise ValueError(f"flash_attn_fp8_kv: q holds the last sq of sk positions (sq {sq}, sk {sk})")
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(d)
+    if _fp8_prefill_native(q, k8, v8, kv_scale):
+        return _flash_fwd_fp8(q, k8, v8, kv_scale, sk, scale, window, None, waves, kv2)
+    from . import fp8_kv
+    k = fp8_kv.dequantize(k8, kv_scale[0], q.dtype)
+    v = fp8_kv.dequantize(v8, kv_scale[1], q.dtype)
+    with torch.no_grad():
+        return flash_attn_func(q, k, v, causal=True, softmax_scale=scale, window=window)
+
+
 def flash_attn_paged(q, k_pool, v_pool, page_table, sk, softmax_scale=None, window=0,
                      kv_scale=None, waves=0, kv2=-1):
     """A block of queries over keys that live in pages (the continued prefill
@@ -247,11 +313,13 @@ def flash_attn_paged(q, k_pool, v_pool, page_table, sk, softmax_scale=None, wind
     is pool row ``page_table[i, j // KV_PAGE] * KV_PAGE + j % KV_PAGE``
     (``page_table`` int32 ``[>= b, pages_per_row]``).  No autograd.
 
-    Native 16-bit pools go to the paged forms of the forward kernel
-    (``csrc/flash_attn_fwd.hip``), which read the pages in place.  Everything
-    else (CPU, fp32, other head dims, FP8 pools: uint8 with ``kv_scale`` fp32
-    ``[2, nkv]``) gathers each row's first ``sk`` keys, dequantises FP8 bytes,
-    and runs the contiguous attention on them.  ``waves`` / ``kv2`` force a
+    Native pools go to the paged forms of the forward kernel
+    (``csrc/flash_attn_fwd.hip``), which read the pages in place: 16-bit pools
+    of ``q``'s dtype, and FP8 pools (uint8 e4m3fn bytes with ``kv_scale`` fp32
+    ``[2, nkv]``), which the FP8 forms expand on the way to LDS.  Everything
+    else (CPU, fp32, other head dims, ``EMA_FA_FP8_PREFILL=0``) gathers each
+    row's first ``sk`` keys, dequantises FP8 bytes, and runs the contiguous
+    attention on them.  ``waves`` / ``kv2`` force a
     kernel form (tests), as the ``flash_attn_fwd`` binding takes them."""
     from ..inference.paged import KV_PAGE, gather_rows
     _check_window(window, True)
@@ -278,6 +346,8 @@ def flash_attn_paged(q, k_pool, v_pool, page_table, sk, softmax_scale=None, wind
                              None, None, None, None, window=int(window), page_table=page_table,
                              waves=int(waves), kv2=int(kv2))
         return out
+    if fp8 and _fp8_prefill_native(q, k_pool, v_pool, kv_scale):
+        return _flash_fwd_fp8(q, k_pool, v_pool, kv_scale, sk, scale, window, page_table, waves, kv2)
     k = torch.stack([gather_rows(k_pool[0], page_table[i], sk) for i in range(b)])
     v = torch.stack([gather_rows(v_pool[0], page_table[i], sk) for i in range(b)])
     if fp8:
