@@ -21,6 +21,11 @@ CSRC = os.path.join(PKG, "csrc")
 BUILD = os.path.join(os.path.dirname(PKG), "build", "csrc")
 ARCH = os.environ.get("EMA_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+# Newer kernels are compiled without the packed fp32 VALU forms (v_pk_*_f32):
+# scalar fp32 math, the same values.  The older files keep their flags, so
+# their instruction streams do not move.
+NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+NO_PACKED_FP32_SRCS = ("wide_gemm.hip",)
 
 
 def _torch_paths():
@@ -59,7 +64,8 @@ def build_kernels(force=False, jobs=None):
         obj = os.path.join(BUILD, os.path.basename(src) + ".o")
         objs.append(obj)
         if force or _newer(obj, [src] + headers):
-            jobs_list.append([HIPCC, "-c", src, "-o", obj] + common)
+            jobs_list.append([HIPCC, "-c", src, "-o", obj] + common +
+                             NO_PACKED_FP32 * (os.path.basename(src) in NO_PACKED_FP32_SRCS))
     # host-side sources that use ATen / pybind11 / hipBLASLt
     for bsrc in (os.path.join(CSRC, "bindings.cpp"), os.path.join(CSRC, "gemm_lt.cpp")):
         bobj = os.path.join(BUILD, os.path.basename(bsrc) + ".o")

@@ -955,14 +955,15 @@ void kv_store_fp8(const at::Tensor& k, const at::Tensor& v, at::Tensor kcache, a
 // qkv decode projection: returns the rotated q [M, ng * r * hd]; k / v rows go
 // to kcache / vcache [L, B, ng, hd] (views at the batch offset) at the slot
 // `slot_t` (int64 device scalar, or M > 1 elements: row m's slot) or `slot`.
-at::Tensor skinny_qkv_rope_cache(const at::Tensor& x, const at::Tensor& w,
+// wide_fb < 0: the skinny kernel; else the 33-64-row kernel with that split
+static at::Tensor qkv_rope_cache(const at::Tensor& x, const at::Tensor& w,
                                  const c10::optional<at::Tensor>& norm_w, double eps, int64_t ng,
                                  int64_t r, int64_t hd, const at::Tensor& cos,
                                  const at::Tensor& sin, const at::Tensor& pos, at::Tensor kcache,
                                  at::Tensor vcache, const c10::optional<at::Tensor>& slot_t,
                                  int64_t slot, bool packed,
                                  const c10::optional<at::Tensor>& w_scale,
-                                 const c10::optional<at::Tensor>& kv_scale) {
+                                 const c10::optional<at::Tensor>& kv_scale, int wide_fb) {
   auto p = skinny_args(x, w, norm_w, eps, packed, w_scale);
   const int64_t N = w.size(0);
   TORCH_CHECK(N == ng * (r + 2) * hd && hd % 8 == 0, "skinny qkv: w rows != ng * (r + 2) * hd");
@@ -971,7 +972,8 @@ at::Tensor skinny_qkv_rope_cache(const at::Tensor& x, const at::Tensor& w,
   if (kv_scale) p.kv_scale = kv_scale_ptr(*kv_scale, ng, x);
   else TORCH_CHECK(kcache.scalar_type() != at::kByte && vcache.scalar_type() != at::kByte,
                    "skinny qkv: an FP8 (uint8) cache needs its kv_scale tensor");
-  TORCH_CHECK(ema::skinny_gemm_supported(p.M, N, p.K), "skinny qkv: unsupported shape");
+  TORCH_CHECK(wide_fb < 0 ? ema::skinny_gemm_supported(p.M, N, p.K)
+                          : ema::wide_gemm_supported(p.M, N, p.K), "skinny qkv: unsupported shape");
   TORCH_CHECK(cos.is_cuda() && sin.is_cuda() && cos.scalar_type() == at::kFloat &&
               sin.scalar_type() == at::kFloat && cos.is_contiguous() && sin.is_contiguous() &&
               cos.size(-1) == hd / 2, "skinny qkv: rope tables fp32 [max_pos, hd/2]");
@@ -1008,8 +1010,95 @@ at::Tensor skinny_qkv_rope_cache(const at::Tensor& x, const at::Tensor& w,
   p.vcache = vcache.data_ptr();
   p.c_ss = kcache.stride(0);
   p.c_sb = kcache.stride(1);
-  ema::skinny_gemm_ex(p, 3, dtype_code(x), cur_stream());
+  if (wide_fb < 0) ema::skinny_gemm_ex(p, 3, dtype_code(x), cur_stream());
+  else ema::wide_gemm_ex(p, 3, dtype_code(x), wide_fb, cur_stream());
   return q;
+}
+
+at::Tensor skinny_qkv_rope_cache(const at::Tensor& x, const at::Tensor& w,
+                                 const c10::optional<at::Tensor>& norm_w, double eps, int64_t ng,
+                                 int64_t r, int64_t hd, const at::Tensor& cos,
+                                 const at::Tensor& sin, const at::Tensor& pos, at::Tensor kcache,
+                                 at::Tensor vcache, const c10::optional<at::Tensor>& slot_t,
+                                 int64_t slot, bool packed,
+                                 const c10::optional<at::Tensor>& w_scale,
+                                 const c10::optional<at::Tensor>& kv_scale) {
+  return qkv_rope_cache(x, w, norm_w, eps, ng, r, hd, cos, sin, pos, kcache, vcache, slot_t, slot,
+                        packed, w_scale, kv_scale, -1);
+}
+
+// ---------------------------------------------------------------- wide GEMM (decode, 33-64 rows)
+// csrc/wide_gemm.hip.  w is always a decode-packed copy with half_tail = 0
+// (16-bit, or e4m3 / MXFP4 with w_scale as in the skinny bindings); fb = feature
+// blocks per workgroup (1, 2, 4, 8; 0: the host's choice).
+bool wide_gemm_supported(int64_t M, int64_t N, int64_t K) {
+  return ema::wide_gemm_supported(M, N, K);
+}
+
+// the output rows: a fresh [M, N], or `out` (at least [M, N], unit column
+// stride, 16-B aligned rows), of which [:M, :N] is written and returned
+static at::Tensor wide_out(const at::Tensor& x, const c10::optional<at::Tensor>& out, int64_t M,
+                           int64_t N) {
+  if (!out) return at::empty({M, N}, x.options());
+  TORCH_CHECK(out->is_cuda() && out->device() == x.device() && out->scalar_type() == x.scalar_type() &&
+              out->dim() == 2 && out->size(0) >= M && out->size(1) >= N && out->stride(1) == 1 &&
+              out->stride(0) % 8 == 0, "wide: out must hold [M, N] rows of the x dtype");
+  check_vec_aligned(*out, "out");
+  return out->narrow(0, 0, M).narrow(1, 0, N);
+}
+
+static int wide_fb(int64_t fb) {
+  TORCH_CHECK(fb == 0 || fb == 1 || fb == 2 || fb == 4 || fb == 8, "wide: fb must be 0, 1, 2, 4 or 8");
+  return (int)fb;
+}
+
+at::Tensor wide_gemm(const at::Tensor& x, const at::Tensor& w,
+                     const c10::optional<at::Tensor>& res,
+                     const c10::optional<at::Tensor>& w_scale, int64_t fb,
+                     const c10::optional<at::Tensor>& out) {
+  auto p = skinny_args(x, w, c10::nullopt, 0.0, true, w_scale);
+  const int64_t N = w.size(0);
+  TORCH_CHECK(ema::wide_gemm_supported(p.M, N, p.K), "wide_gemm: unsupported shape");
+  auto y = wide_out(x, out, p.M, N);
+  p.N = (int)N;
+  p.y = y.data_ptr();
+  p.ldy = y.stride(0);
+  if (res) {
+    TORCH_CHECK(res->is_cuda() && res->scalar_type() == x.scalar_type() && res->dim() == 2 &&
+                res->size(0) == p.M && res->size(1) == N && res->stride(1) == 1 &&
+                res->stride(0) % 8 == 0, "wide_gemm: residual must be [M, N] rows of the x dtype");
+    check_vec_aligned(*res, "res");
+    p.res = res->data_ptr();
+    p.ldr = res->stride(0);
+  }
+  ema::wide_gemm_ex(p, res ? 1 : 0, dtype_code(x), wide_fb(fb), cur_stream());
+  return y;
+}
+
+at::Tensor wide_glu(const at::Tensor& x, const at::Tensor& w1, int64_t kind,
+                    const c10::optional<at::Tensor>& w_scale, int64_t fb,
+                    const c10::optional<at::Tensor>& out) {
+  auto p = skinny_args(x, w1, c10::nullopt, 0.0, true, w_scale);
+  const int64_t F = w1.size(0) / 2;
+  TORCH_CHECK(w1.size(0) == 2 * F && F % 8 == 0 && kind >= 0 && kind <= 3 &&
+              ema::wide_gemm_supported(p.M, 2 * F, p.K), "wide_glu: unsupported shape");
+  auto y = wide_out(x, out, p.M, F);
+  p.N = (int)F;
+  p.y = y.data_ptr();
+  p.ldy = y.stride(0);
+  p.act = (int)kind;
+  ema::wide_gemm_ex(p, 2, dtype_code(x), wide_fb(fb), cur_stream());
+  return y;
+}
+
+at::Tensor wide_qkv_rope_cache(const at::Tensor& x, const at::Tensor& w, int64_t ng, int64_t r,
+                               int64_t hd, const at::Tensor& cos, const at::Tensor& sin,
+                               const at::Tensor& pos, at::Tensor kcache, at::Tensor vcache,
+                               const c10::optional<at::Tensor>& slot_t, int64_t slot,
+                               const c10::optional<at::Tensor>& w_scale,
+                               const c10::optional<at::Tensor>& kv_scale, int64_t fb) {
+  return qkv_rope_cache(x, w, c10::nullopt, 0.0, ng, r, hd, cos, sin, pos, kcache, vcache, slot_t,
+                        slot, true, w_scale, kv_scale, wide_fb(fb));
 }
 
 // ---------------------------------------------------------------- decode attention
@@ -1686,6 +1775,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("cos"), py::arg("sin"), py::arg("pos"), py::arg("kcache"), py::arg("vcache"),
         py::arg("slot_t"), py::arg("slot"), py::arg("packed") = false,
         py::arg("w_scale") = py::none(), py::arg("kv_scale") = py::none());
+  m.def("wide_gemm_supported", &wide_gemm_supported);
+  m.def("wide_gemm_split", &ema::wide_gemm_split, py::arg("nblocks"));
+  m.def("wide_gemm", &wide_gemm, py::arg("x"), py::arg("w_packed"), py::arg("res") = py::none(),
+        py::arg("w_scale") = py::none(), py::arg("fb") = 0, py::arg("out") = py::none());
+  m.def("wide_glu", &wide_glu, py::arg("x"), py::arg("w1_packed"), py::arg("kind"),
+        py::arg("w_scale") = py::none(), py::arg("fb") = 0, py::arg("out") = py::none());
+  m.def("wide_qkv_rope_cache", &wide_qkv_rope_cache, py::arg("x"), py::arg("w_packed"),
+        py::arg("ng"), py::arg("r"), py::arg("hd"), py::arg("cos"), py::arg("sin"), py::arg("pos"),
+        py::arg("kcache"), py::arg("vcache"), py::arg("slot_t"), py::arg("slot"),
+        py::arg("w_scale") = py::none(), py::arg("kv_scale") = py::none(), py::arg("fb") = 0);
   m.def("transpose16", &transpose16);
   m.def("transpose16_supported", &transpose16_supported);
 }

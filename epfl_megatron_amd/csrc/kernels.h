@@ -450,6 +450,14 @@ struct SkinnyArgs {
 void skinny_gemm_ex(const SkinnyArgs& p, int epi, int dt, hipStream_t s);
 int skinny_glu_half_tail(int64_t F, int64_t K, bool norm, int64_t M);
 
+// ---- wide_gemm.hip: the same products for 33-64 rows (X through LDS) ----
+// SkinnyArgs as above with packed = 1 (half_tail = 0 packs only) and no
+// norm_w; fb = feature blocks per workgroup (1, 2, 4, 8; K slices = 8 / fb),
+// 0 = wide_gemm_split(number of 16-row W blocks).
+bool wide_gemm_supported(int64_t M, int64_t N, int64_t K);
+int wide_gemm_split(int64_t nblocks);
+void wide_gemm_ex(const SkinnyArgs& p, int epi, int dt, int fb, hipStream_t s);
+
 // ---- transpose.hip -------------------------------------------------------------------------------
 // dst[cols, rows] = src[rows, cols]^T for 16-bit elements; rows, cols multiples of 64.
 bool transpose16_supported(int64_t rows, int64_t cols);

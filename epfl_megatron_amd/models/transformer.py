@@ -51,6 +51,19 @@ from .utils import attention_mask_func, erf_gelu
 # decode attention -> [dense + residual] -> [RMSNorm + fc1 + GLU] ->
 # [fc2 + residual].  EMA_DECODE_FUSED=0 keeps the unfused kernels.
 _DECODE_FUSED = os.environ.get("EMA_DECODE_FUSED", "1") != "0"
+# 33-64 rows can run the same fused step through csrc/wide_gemm.hip (X staged
+# in LDS).  EMA_WIDE_GEMM: "auto" (default) takes it under the quantised-weight
+# flags only, whose packed copies nothing else reads at these row counts; with
+# 16-bit weights its forms lose to hipBLASLt on four of the five Llama-2-7B
+# products (profiles/r19a_wide_decode.txt), so those steps stay where they
+# were.  "1": always; "0": never.
+_WIDE_GEMM = os.environ.get("EMA_WIDE_GEMM", "auto")
+
+
+def _wide_on():
+    return _WIDE_GEMM == "1" or (_WIDE_GEMM != "0" and (_FP8_WEIGHTS or _MXFP4_WEIGHTS))
+
+
 # FP8 weight-only decode (--inference_fp8_weights, opt-in): the fused decode
 # layer streams its four products' weights as per-row-scaled e4m3
 # (ops/fp8_weights.py) wherever the shape packs; the LM head, the prefill and
@@ -703,7 +716,8 @@ class ParallelTransformerLayer(MegatronModule):
         no sequence parallelism: a decode step has one row per sequence)."""
         if not (_DECODE_FUSED and ip is not None and not torch.is_grad_enabled()
                 and hidden_states.is_cuda and hidden_states.dim() == 3
-                and hidden_states.shape[0] == 1 and hidden_states.shape[1] <= 32
+                and hidden_states.shape[0] == 1
+                and hidden_states.shape[1] <= (64 if _wide_on() else 32)
                 and hidden_states.dtype in (torch.bfloat16, torch.float16)
                 and self._fused_residual_ok()):
             return False
@@ -726,6 +740,14 @@ class ParallelTransformerLayer(MegatronModule):
         if any(w.dtype != hidden_states.dtype or not w.is_contiguous() for w in ws):
             return False
         F2 = w1.shape[0]
+        if b > 32:
+            # 33-64 rows: the X-through-LDS kernel (csrc/wide_gemm.hip) reads
+            # the decode-packed copies only
+            return (F2 % 16 == 0 and decode_pack.ENABLED
+                    and all(decode_pack.packable(w) for w in (wq, wo, w1, w2))
+                    and C.wide_gemm_supported(b, wq.shape[0], H)
+                    and C.wide_gemm_supported(b, H, wo.shape[1])
+                    and C.wide_gemm_supported(b, F2, H) and C.wide_gemm_supported(b, H, F2 // 2))
         return (F2 % 16 == 0 and C.skinny_gemm_supported(b, wq.shape[0], H)
                 and C.skinny_gemm_supported(b, H, wo.shape[1])
                 and C.skinny_gemm_supported(b, F2, H) and C.skinny_gemm_supported(b, H, F2 // 2))
@@ -770,8 +792,11 @@ class ParallelTransformerLayer(MegatronModule):
         # the un-normed two-row-block forms (the normed ones spill their 2 x 16
         # X fragments: profiles/r4ai_skinny_mb.txt)
         sep = b > 16
+        # 33-64 rows: the same route through the wide kernel's forms, which
+        # read the packs without a half-unit tail
+        wide = b > 32
         # the half-unit tail of the form that will run (normed for <= 16 rows)
-        tail = C.skinny_glu_half_tail(w1.shape[0] // 2, w1.shape[1], not sep, b)
+        tail = 0 if wide else C.skinny_glu_half_tail(w1.shape[0] // 2, w1.shape[1], not sep, b)
 
         def stream(w, **form):
             """(weight to stream, its e4m3 row scales / e8m0 block scales or
@@ -789,11 +814,16 @@ class ParallelTransformerLayer(MegatronModule):
         (pq, sq), (po, so) = stream(wq), stream(wo)
         (p1, s1), (p2, s2) = stream(w1, glu=True, half_tail=tail), stream(w2)
         xq = rms_norm(x, ln1.weight, ln1.eps) if sep else x
-        q = C.skinny_qkv_rope_cache(xq, wq if pq is None else pq, None if sep else ln1.weight,
-                                    ln1.eps, ng, r, hd,
-                                    cos, sin, pos, kc, vc,
-                                    ip.device_offset if graph else None, 0 if graph else s0,
-                                    pq is not None, sq, *(() if kvs is None else (kvs,)))
+        if wide:
+            q = C.wide_qkv_rope_cache(xq, pq, ng, r, hd, cos, sin, pos, kc, vc,
+                                      ip.device_offset if graph else None, 0 if graph else s0,
+                                      sq, kvs)
+        else:
+            q = C.skinny_qkv_rope_cache(xq, wq if pq is None else pq, None if sep else ln1.weight,
+                                        ln1.eps, ng, r, hd,
+                                        cos, sin, pos, kc, vc,
+                                        ip.device_offset if graph else None, 0 if graph else s0,
+                                        pq is not None, sq, *(() if kvs is None else (kvs,)))
         q4 = q.view(b, 1, ng * r, hd)
         if table is not None:
             o = flash_decode_cached(q4, kmem.transpose(0, 1), vmem.transpose(0, 1),
@@ -818,6 +848,14 @@ class ParallelTransformerLayer(MegatronModule):
         # (one persistent launch with grid barriers for these three products was
         # measured 2.6x slower than the three launches: profiles/r3x_decode_mlp_fused.txt)
         first = state.get_tensor_model_parallel_rank() == 0
+        if wide:
+            h2 = C.wide_gemm(o.reshape(b, -1), po, x if first else None, so)
+            h2 = tp.reduce_from_tensor_model_parallel_region(h2)
+            y = C.wide_glu(rms_norm(h2, ln2.weight, ln2.eps), p1,
+                           tp.layers._GLU_KIND[mlp.glu_activation], s1)
+            h3 = C.wide_gemm(y, p2, h2 if first else None, s2)
+            h3 = tp.reduce_from_tensor_model_parallel_region(h3)
+            return h3.view(1, b, H)
         h2 = C.skinny_norm_gemm(o.reshape(b, -1), wo if po is None else po, None, 0.0,
                                 x if first else None, po is not None, so)
         h2 = tp.reduce_from_tensor_model_parallel_region(h2)

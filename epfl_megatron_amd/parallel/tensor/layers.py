@@ -899,6 +899,10 @@ def glu_mlp(input_, w1, w2, glu_kind, *, sequence_parallel, tp_async_allreduce,
 # streaming HIP GEMM (csrc/skinny_gemm.hip) instead of hipBLASLt's skinny
 # tiles (profiles/r2c_skinny_gemm.txt).  EMA_SKINNY_GEMM=0 disables it.
 _SKINNY = os.environ.get("EMA_SKINNY_GEMM", "1") != "0"
+# 33-64 rows on the 16-bit pack: csrc/wide_gemm.hip only when forced
+# (EMA_WIDE_GEMM=1): hipBLASLt is faster on the LM head
+# (profiles/r19a_wide_decode.txt)
+_WIDE = os.environ.get("EMA_WIDE_GEMM", "auto") == "1"
 
 
 def _skinny_linear(input_, weight, bias, sequence_parallel):
@@ -909,6 +913,16 @@ def _skinny_linear(input_, weight, bias, sequence_parallel):
     k = input_.shape[-1]
     m = input_.numel() // k
     n = weight.shape[0]
+    if 32 < m <= 64:
+        # 33-64 rows: the X-through-LDS kernel on the decode-packed copy
+        # (csrc/wide_gemm.hip under EMA_WIDE_GEMM=1, else hipBLASLt)
+        wp = decode_pack.packed(weight) if _WIDE and weight.is_contiguous() else None
+        if wp is None or not ext().wide_gemm_supported(m, n, k):
+            return None
+        x2 = input_.reshape(m, k)
+        out = ext().wide_gemm(x2 if x2.is_contiguous() else x2.contiguous(), wp)
+        out = out.view(*input_.shape[:-1], n)
+        return out if bias is None else out + bias
     if m > 32 or not weight.is_contiguous() or not ext().skinny_gemm_supported(m, n, k):
         return None
     # K = 4096 / 8192 run the persistent skinny kernel, faster than hipBLASLt up
