@@ -67,6 +67,7 @@ from collections import deque
 import torch
 
 from ..parallel import state
+from . import kv_cache
 from .hip_graph import broadcast_seed_offset
 from .paged import KV_PAGE, PagePool, PrefixCache, pages_for, physical_slots
 
@@ -124,8 +125,7 @@ class RaggedGreedyDecoder:
         if state.model_parallel_is_initialized() and \
                 state.get_pipeline_model_parallel_world_size() > 1:
             raise NotImplementedError("the ragged decode loop needs the whole model (PP = 1)")
-        from ..models import transformer
-        if transformer._FP8_KV and transformer._FP8_KV_CALIBRATE:
+        if kv_cache.FP8_KV and kv_cache.FP8_KV_CALIBRATE:
             raise NotImplementedError(
                 "ragged decode refills rows one at a time: prompt calibration of the FP8 KV "
                 "scales (--inference_fp8_kv_calibrate) would rescale the other rows' cached "
@@ -147,7 +147,7 @@ class RaggedGreedyDecoder:
         self.active = z(batch, torch.int32)
         self.tail_counter = z(1, torch.int32)
         # paged cache: the table lives next to the state it indexes
-        self.paged = getattr(inference_params, "page_table", None) is not None
+        self.paged = inference_params.page_table is not None
         if self.paged:
             if batch > self.ip.page_table.shape[0]:
                 raise ValueError("batch exceeds the rows of the page table")
@@ -465,7 +465,7 @@ class ContinuousBatcher:
             raise ValueError("poll_every must be >= 1")
         if prefill_chunk is not None and int(prefill_chunk) < 2:
             raise ValueError("prefill_chunk must be >= 2 (None: the whole prompt in one call)")
-        if prefix_cache and getattr(ip, "page_table", None) is None:
+        if prefix_cache and ip.page_table is None:
             raise ValueError("prefix_cache needs a paged KV cache (InferenceParams(kv_pages=...))")
         self.model, self.ip, self.batch, self.capacity = model, ip, batch, capacity
         self.poll_every = poll_every
@@ -482,7 +482,7 @@ class ContinuousBatcher:
         self.rows = [None] * batch  # request id, first token per busy row
         self.primed = []        # (row, position, max_new) of every prime, for inspection
         self.replays = 0
-        self.paged = getattr(ip, "page_table", None) is not None
+        self.paged = ip.page_table is not None
         self.pool = PagePool(ip.kv_pages) if self.paged else None
         self.row_pages = [None] * batch  # pages held by each busy row
         self.page_log = []      # (request id, row, pages) of every admission

@@ -1,9 +1,10 @@
 """Incremental (KV-cached) forward for generation (reference
 ``megatron/text_generation/forward_step.py``).
 
-``InferenceParams`` owns the per-layer KV caches (allocated lazily by each
-attention layer as ``[max_seq, max_batch, nkv_per_tp, hd]`` — GQA keys stay at
-``nkv`` heads, already rotated) and the running sequence / batch offsets.
+``InferenceParams`` owns the per-layer KV caches (allocated on each attention
+layer's first call by ``inference/kv_cache.py`` as ``[max_seq, max_batch,
+nkv_per_tp, hd]`` — GQA keys stay at ``nkv`` heads, already rotated) and the
+running sequence / batch offsets.
 ``ForwardStep`` runs one model call per generation step across pipeline
 stages; when ``batch x new_tokens`` exceeds
 ``--inference_batch_times_seqlen_threshold`` the batch is split into
@@ -44,6 +45,9 @@ class InferenceParams:
         # > 0 continues row batch_size_offset over the keys its table already
         # names (a shared prefix, an earlier chunk); clear, it raises
         self.continue_prefill = False
+        # paged cache only: (key, pool rows) of the prefill call in flight, which
+        # its first layer computes for the others (inference/kv_cache.py)
+        self._prefill_slots = (None, None)
         self.key_value_memory_dict = {}
         # hipGraph decode (inference/hip_graph.py): the cache slot of the new
         # token (int64 [1]) and the valid key count (int32 [1]) on the device;

@@ -84,7 +84,7 @@ def _pp_stage():
 
 
 def _check_unpaged(inference_params, who):
-    if getattr(inference_params, "page_table", None) is not None:
+    if inference_params.page_table is not None:
         raise NotImplementedError(
             f"{who} moves the batch in lockstep (one cache slot for all rows) and is not "
             "paged: a paged KV cache is served by the ragged decoders of "

@@ -35,11 +35,12 @@ from ..ops.norms import RMSNorm, MixedFusedLayerNorm, _param_sync, rms_norm
 from ..ops.rope import rope_table, apply_rope_ref, rope_qkv_inplace, rope_qkv
 from ..ops._ext import use_native, ext
 from ..parallel.context import chunk_position_ids, ring_attention
-from ..ops.attention import (flash_attn_qkvpacked, flash_attn_func, flash_attn_paged,
-                             flash_attn_fp8_kv, flash_decode_cached)
+from ..ops.attention import flash_attn_qkvpacked
 from ..ops.activations import glu, bias_gelu, gelu
-from ..ops import decode_pack, fp8_kv, fp8_weights, mxfp4_weights
+from ..ops import decode_pack, fp8_weights, mxfp4_weights
 from ..ops.softmax import FusedScaleMaskSoftmax
+from ..inference import kv_cache
+from ..inference.kv_cache import LayerKV, set_fp8_kv_cache
 from .enums import AttnMaskType, AttnType, LayerType, ModelType, PositionEmbeddingType
 from .module import MegatronModule
 from .utils import attention_mask_func, erf_gelu
@@ -89,22 +90,11 @@ def set_mxfp4_weights(on):
     _MXFP4_WEIGHTS = bool(on)
 
 
-# FP8 KV cache (--inference_fp8_kv_cache, opt-in): caches allocated under the
-# switch hold e4m3 bytes with a scale per KV head (ops/fp8_kv.py); the decode
-# steps read them in csrc/flash_decode.hip's FP8 forms.  With calibration
-# (--inference_fp8_kv_calibrate) the prefill that restarts a cache sets the
-# scales from the prompt; else they stay 1.0.
-_FP8_KV = os.environ.get("EMA_FP8_KV", "0") == "1"
-_FP8_KV_CALIBRATE = os.environ.get("EMA_FP8_KV_CALIBRATE", "0") == "1"
-
-
-def set_fp8_kv_cache(on, calibrate=None):
-    """Switch the FP8 KV cache for every cache allocated from now on (and,
-    with ``calibrate``, the prompt calibration of its scales)."""
-    global _FP8_KV, _FP8_KV_CALIBRATE
-    _FP8_KV = bool(on)
-    if calibrate is not None:
-        _FP8_KV_CALIBRATE = bool(calibrate)
+def __getattr__(name):
+    # the FP8 KV cache switches (set_fp8_kv_cache) live with the cache
+    if name in ("_FP8_KV", "_FP8_KV_CALIBRATE"):
+        return getattr(kv_cache, name[1:])
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def _linear_kwargs(args):
@@ -350,178 +340,6 @@ class ParallelAttention(MegatronModule):
     def _expand_kv(self, t):
         return t.repeat_interleave(self.q_per_group, dim=2) if self.q_per_group > 1 else t
 
-    def _allocate_kv(self, max_len, max_batch, device):
-        shape = (max_len, max_batch, self.num_groups_per_partition,
-                 self.hidden_size_per_attention_head)
-        if _FP8_KV:  # e4m3 bytes (zeroed: an unwritten row must not read as NaN)
-            return (torch.zeros(shape, dtype=torch.uint8, device=device),
-                    torch.zeros(shape, dtype=torch.uint8, device=device))
-        return (torch.empty(shape, dtype=self.params_dtype, device=device),
-                torch.empty(shape, dtype=self.params_dtype, device=device))
-
-    def _kv_memory(self, ip, device):
-        """This layer's (K, V) cache on ``ip``, allocated on first use: a column
-        per row, or with ``ip.kv_pages`` one pool ``[kv_pages * KV_PAGE, 1, nkv,
-        hd]`` each (``inference/paged.py``)."""
-        if self.layer_number not in ip.key_value_memory_dict:
-            if getattr(ip, "page_table", None) is not None:
-                from ..inference.paged import KV_PAGE
-                shape = (ip.kv_pages * KV_PAGE, 1)
-            else:
-                shape = (ip.max_sequence_len, ip.max_batch_size)
-            ip.key_value_memory_dict[self.layer_number] = self._allocate_kv(*shape, device)
-        return ip.key_value_memory_dict[self.layer_number]
-
-    def _paged_forward(self, q, k, v, kmem, vmem, attention_mask, ip):
-        """``_inference_forward`` over a paged cache (16-bit or FP8 pools).  A
-        decode step with device slots writes row ``m``'s K / V at the pool row
-        ``ip.device_offset[m]`` (kept physical by the ragged decoders) and reads
-        through ``ip.page_table``; the whole-prompt prefill of one row scatters
-        its rows to the pool by the row's table, on the device, and attends
-        over the fresh K and V.  With ``ip.continue_prefill`` set, a prefill at
-        ``sequence_len_offset = s0 > 0`` continues the row: its ``sq`` rows go
-        to the pool rows of the positions ``s0 .. s0 + sq - 1`` and the queries
-        attend over the row's ``s0 + sq`` keys through the table
-        (``flash_attn_paged``); the caller vouches that the table covers them
-        and that the first ``s0`` are valid (a shared prefix, an earlier
-        chunk).  Nothing else is supported."""
-        from ..inference.paged import KV_PAGE, gather_rows, physical_slots
-        s0, b0 = ip.sequence_len_offset, ip.batch_size_offset
-        sq, b = q.shape[:2]
-        fp8 = kmem.dtype == torch.uint8
-        sc = self._kv_scales(ip, q.device) if fp8 else None
-        table = ip.page_table[b0:b0 + b]
-        if getattr(ip, "device_offset", None) is not None and sq == 1:
-            if q.is_cuda and not (use_native(q) and q.shape[-1] in (64, 128)):
-                raise NotImplementedError("hipGraph decode needs the native decode attention "
-                                          "kernel (GPU, bf16/fp16, head_dim 64 or 128)")
-            slots = ip.device_offset
-            if slots.numel() != b:
-                raise NotImplementedError(
-                    "a paged KV cache needs one cache slot per row (the ragged decoders of "
-                    "inference/continuous.py): the lockstep decoders of inference/hip_graph.py "
-                    "are not paged; use kv_pages=None")
-            if fp8 and fp8_kv.store_native_ok(k) and fp8_kv.store_native_ok(v):
-                # the pool as a stride-0 batch view: row m lands at slots[m]
-                fp8_kv.store(k, v, kmem.expand(-1, b, -1, -1), vmem.expand(-1, b, -1, -1), sc,
-                             slot_t=slots)
-            elif fp8:
-                kmem[slots, 0] = fp8_kv.quantize(k[0], sc[0])
-                vmem[slots, 0] = fp8_kv.quantize(v[0], sc[1])
-            else:
-                kmem[slots, 0] = k[0]
-                vmem[slots, 0] = v[0]
-            o = flash_decode_cached(q.transpose(0, 1), kmem.transpose(0, 1), vmem.transpose(0, 1),
-                                    ip.device_kv_len, window=self._window(ip.max_sequence_len),
-                                    kv_scale=sc, page_table=table, capacity=ip.max_sequence_len)
-            return o.transpose(0, 1).reshape(sq, b, -1)
-        why = None
-        if sq == 1:
-            why = "a decode step without device slots (the eager KV-cached loop)"
-        elif s0 > 0 and not getattr(ip, "continue_prefill", False):
-            why = "a prefill that continues a cached sequence (sequence_len_offset > 0)"
-        elif b > 1:
-            why = "a prefill of more than one row"
-        elif fp8 and _FP8_KV_CALIBRATE:
-            why = "prompt calibration of the FP8 KV scales (--inference_fp8_kv_calibrate)"
-        if why is not None:
-            raise NotImplementedError(f"paged KV cache: {why} is not supported (only the "
-                                      "whole-prompt prefill of one row and the ragged decode "
-                                      "step are); use kv_pages=None")
-        # the prompt's rows go to the pool rows its table names: device-side indices
-        # (computed by the first layer of a prefill and shared by the others: the
-        # table's version counter moves with every write to it)
-        key = (b0, s0, sq, id(ip.page_table), ip.page_table._version)
-        if getattr(ip, "_prefill_slots", (None,))[0] != key:
-            ip._prefill_slots = (key, physical_slots(table[0],
-                                                     torch.arange(s0, s0 + sq, device=k.device)))
-        idx = ip._prefill_slots[1]
-        if fp8 and fp8_kv.store_native_ok(k) and fp8_kv.store_native_ok(v):
-            p0 = 0
-            while p0 < sq:  # a page's rows are consecutive in the pool: cut at page edges
-                p1 = min(sq, ((s0 + p0) // KV_PAGE + 1) * KV_PAGE - s0)
-                fp8_kv.store(k[p0:p1], v[p0:p1], kmem, vmem, sc, slot_t=idx[p0:p0 + 1])
-                p0 = p1
-        elif fp8:
-            kmem.index_copy_(0, idx, fp8_kv.quantize(k, sc[0]))
-            vmem.index_copy_(0, idx, fp8_kv.quantize(v, sc[1]))
-        else:
-            kmem.index_copy_(0, idx, k)
-            vmem.index_copy_(0, idx, v)
-        if s0 > 0:  # continued: the first s0 keys are in the pages only
-            if self.use_flash_attn:
-                o = flash_attn_paged(q.transpose(0, 1), kmem.transpose(0, 1), vmem.transpose(0, 1),
-                                     table, s0 + sq, window=self._window(s0 + sq), kv_scale=sc)
-                return o.transpose(0, 1).reshape(sq, b, -1)
-            keys, vals = (gather_rows(m, table[0], s0 + sq) for m in (kmem, vmem))
-            if fp8:
-                keys = fp8_kv.dequantize(keys, sc[0], q.dtype)
-                vals = fp8_kv.dequantize(vals, sc[1], q.dtype)
-            return self.core_attention(q, self._expand_kv(keys), self._expand_kv(vals),
-                                       attention_mask)
-        if self.use_flash_attn:
-            o = flash_attn_func(q.transpose(0, 1), k.transpose(0, 1), v.transpose(0, 1),
-                                causal=True, window=self._window(sq))
-            return o.transpose(0, 1).reshape(sq, b, -1)
-        return self.core_attention(q, self._expand_kv(k), self._expand_kv(v), attention_mask)
-
-    def _kv_scales(self, ip, device):
-        """This layer's FP8 cache scales (fp32 [2, nkv_per_tp], 1.0 until set),
-        kept on the inference params next to the cache."""
-        d = getattr(ip, "kv_scale_dict", None)
-        if d is None:
-            d = ip.kv_scale_dict = {}
-        if self.layer_number not in d:
-            d[self.layer_number] = fp8_kv.new_scales(self.num_groups_per_partition, device)
-        return d[self.layer_number]
-
-    def _fp8_kv_forward(self, q, k, v, kmem, vmem, attention_mask, ip):
-        """``_inference_forward`` over an FP8 cache: the new rows go through the
-        quantising store; the restart prefill attends over its fresh 16-bit K
-        and V, a decode step on the native path reads the bytes in the FP8
-        decode kernel, a continued prefill on it in the FP8 forms of the
-        forward kernel, and everything else dequantises the slice it needs."""
-        s0, b0 = ip.sequence_len_offset, ip.batch_size_offset
-        sq, b = q.shape[:2]
-        sc = self._kv_scales(ip, q.device)
-        kc, vc = kmem[:, b0:b0 + b], vmem[:, b0:b0 + b]
-        native = use_native(q) and q.shape[-1] in (64, 128)
-        if getattr(ip, "device_offset", None) is not None and sq == 1:
-            if q.is_cuda and not native:
-                raise NotImplementedError("hipGraph decode needs the native decode attention "
-                                          "kernel (GPU, bf16/fp16, head_dim 64 or 128)")
-            fp8_kv.store(k, v, kc, vc, sc, slot_t=ip.device_offset)
-            o = flash_decode_cached(q.transpose(0, 1), kc.transpose(0, 1), vc.transpose(0, 1),
-                                    ip.device_kv_len, window=self._window(kc.shape[0]),
-                                    kv_scale=sc)
-            return o.transpose(0, 1).reshape(sq, b, -1)
-        if s0 == 0 and b0 == 0 and _FP8_KV_CALIBRATE:
-            fp8_kv.calibrate_(sc, k, v)
-        fp8_kv.store(k, v, kc, vc, sc, slot=s0)
-        if sq == 1 and native and self.use_flash_attn:
-            o = flash_decode_cached(q.transpose(0, 1), kc[:s0 + 1].transpose(0, 1),
-                                    vc[:s0 + 1].transpose(0, 1), None,
-                                    window=self._window(s0 + 1), kv_scale=sc)
-            return o.transpose(0, 1).reshape(sq, b, -1)
-        if s0 > 0 and native and self.use_flash_attn:
-            # continued prefill: the FP8 forms of the forward kernel read the
-            # stored bytes (the new rows' own included) in place
-            o = flash_attn_fp8_kv(q.transpose(0, 1), kc[:s0 + sq].transpose(0, 1),
-                                  vc[:s0 + sq].transpose(0, 1), sc,
-                                  window=self._window(s0 + sq))
-            return o.transpose(0, 1).reshape(sq, b, -1)
-        if s0 == 0:
-            keys, vals = k, v
-        else:
-            keys = fp8_kv.dequantize(kc[:s0 + sq], sc[0], q.dtype)
-            vals = fp8_kv.dequantize(vc[:s0 + sq], sc[1], q.dtype)
-        if self.use_flash_attn:
-            o = flash_attn_func(q.transpose(0, 1), keys.transpose(0, 1), vals.transpose(0, 1),
-                                causal=True, window=self._window(s0 + sq))
-            return o.transpose(0, 1).reshape(sq, b, -1)
-        return self.core_attention(q, self._expand_kv(keys), self._expand_kv(vals),
-                                   attention_mask)
-
     def _core(self, q, k, v, attention_mask):
         if self.checkpoint_core_attention and self.training:
             return tp.checkpoint(lambda *a: self.core_attention(*a), False, q, k, v,
@@ -582,7 +400,6 @@ class ParallelAttention(MegatronModule):
 
     def _inference_forward(self, mixed, attention_mask, ip, position_ids, rope):
         s0 = ip.sequence_len_offset
-        b0 = ip.batch_size_offset
         if rope is not None and use_native(mixed) and mixed.is_contiguous() and \
                 not (torch.is_grad_enabled() and mixed.requires_grad):
             # one in-place HIP pass over q and k of the fused projection, with
@@ -593,45 +410,17 @@ class ParallelAttention(MegatronModule):
                              rope[0], rope[1], position_ids, offset=s0)
             rope = None
         q, k, v = self._split_qkv(mixed)
-        sq, b = q.shape[:2]
-        kmem, vmem = self._kv_memory(ip, mixed.device)
         if rope is not None:
             # Rotate with the true positions BEFORE caching (fixes D1).
             q = apply_rope_ref(q, rope[0], rope[1], position_ids, offset=s0)
             k = apply_rope_ref(k, rope[0], rope[1], position_ids, offset=s0)
-        if getattr(ip, "page_table", None) is not None:
-            return self._paged_forward(q, k, v, kmem, vmem, attention_mask, ip)
-        if kmem.dtype == torch.uint8:
-            return self._fp8_kv_forward(q, k, v, kmem, vmem, attention_mask, ip)
-        if getattr(ip, "device_offset", None) is not None and sq == 1:
-            # hipGraph decode step (inference/hip_graph.py): cache slot and key
-            # count live in device tensors, so no launch depends on the step
-            # (on the CPU the static-buffer step runs eagerly: reference attention)
-            if q.is_cuda and not (use_native(q) and q.shape[-1] in (64, 128)):
-                raise NotImplementedError("hipGraph decode needs the native decode attention "
-                                          "kernel (GPU, bf16/fp16, head_dim 64 or 128)")
-            kc, vc = kmem[:, b0:b0 + b], vmem[:, b0:b0 + b]
-            if b > 1 and ip.device_offset.numel() == b:
-                # one slot per sequence (ragged decode, inference/continuous.py)
-                rows = torch.arange(b, device=k.device)
-                kc[ip.device_offset, rows] = k[0]
-                vc[ip.device_offset, rows] = v[0]
-            else:
-                kc.index_copy_(0, ip.device_offset, k)
-                vc.index_copy_(0, ip.device_offset, v)
-            o = flash_decode_cached(q.transpose(0, 1), kc.transpose(0, 1), vc.transpose(0, 1),
-                                    ip.device_kv_len, window=self._window(kc.shape[0]))
-            return o.transpose(0, 1).reshape(sq, b, -1)
-        kmem[s0:s0 + sq, b0:b0 + b] = k
-        vmem[s0:s0 + sq, b0:b0 + b] = v
-        keys = kmem[:s0 + sq, b0:b0 + b]
-        vals = vmem[:s0 + sq, b0:b0 + b]
-        if self.use_flash_attn:
-            o = flash_attn_func(q.transpose(0, 1), keys.transpose(0, 1), vals.transpose(0, 1),
-                                causal=True, window=self._window(s0 + sq))
-            return o.transpose(0, 1).reshape(sq, b, -1)
-        return self.core_attention(q, self._expand_kv(keys), self._expand_kv(vals),
-                                   attention_mask)
+        kv = LayerKV(ip, self.layer_number, self.num_groups_per_partition,
+                     self.hidden_size_per_attention_head, self.params_dtype, mixed.device,
+                     *q.shape[:2])
+        kv.write(k, v)
+        return kv.attend(q, k, v, self._window, self.use_flash_attn,
+                         lambda q, keys, vals: self.core_attention(
+                             q, self._expand_kv(keys), self._expand_kv(vals), attention_mask))
 
     def _cross_forward(self, hidden_states, attention_mask, encoder_output):
         kv, _ = self.key_value(encoder_output)
@@ -760,31 +549,16 @@ class ParallelTransformerLayer(MegatronModule):
         x = hidden_states.reshape(b, H)
         if not x.is_contiguous():
             x = x.contiguous()
-        kmem, vmem = sa._kv_memory(ip, x.device)
-        b0, s0 = ip.batch_size_offset, ip.sequence_len_offset
-        table = getattr(ip, "page_table", None)
-        if table is not None:
-            # paged cache (inference/paged.py): the pool as a stride-0 batch view,
-            # so that the QKV epilogue writes row m at the pool row device_offset[m]
-            if getattr(ip, "device_offset", None) is None or ip.device_offset.numel() != b:
-                raise NotImplementedError(
-                    "paged KV cache: a decode step needs one device cache slot per row (the "
-                    "ragged decoders of inference/continuous.py); the eager loop and the "
-                    "lockstep decoders of inference/hip_graph.py are not paged; use "
-                    "kv_pages=None")
-            table = table[b0:b0 + b]
-            kc, vc = kmem.expand(-1, b, -1, -1), vmem.expand(-1, b, -1, -1)
-        else:
-            kc, vc = kmem[:, b0:b0 + b], vmem[:, b0:b0 + b]
-        # FP8 KV cache: the QKV epilogue quantises k / v with these scales
-        kvs = sa._kv_scales(ip, x.device) if kmem.dtype == torch.uint8 else None
+        # the cache operands of the QKV epilogue, which writes the new row (and
+        # quantises it for an FP8 cache)
+        ng, r, hd = sa.num_groups_per_partition, sa.q_per_group, sa.hidden_size_per_attention_head
+        kv = LayerKV(ip, sa.layer_number, ng, hd, sa.params_dtype, x.device, 1, b, fused=True)
         cos, sin = sa._rope(x.device)
         if position_ids is None:
-            pos = torch.full((b, 1), s0, dtype=torch.long, device=x.device)
+            pos = torch.full((b, 1), ip.sequence_len_offset, dtype=torch.long,
+                             device=x.device)
         else:
             pos = position_ids[:, -1:].long()
-        graph = getattr(ip, "device_offset", None) is not None
-        ng, r, hd = sa.num_groups_per_partition, sa.q_per_group, sa.hidden_size_per_attention_head
         # weights in the decode-packed layout when the shape allows (ops/decode_pack.py)
         wq, wo = sa.query_key_value.weight, sa.dense.weight
         w1, w2 = mlp.dense_h_to_4h.weight, mlp.dense_4h_to_h.weight
@@ -815,31 +589,15 @@ class ParallelTransformerLayer(MegatronModule):
         (p1, s1), (p2, s2) = stream(w1, glu=True, half_tail=tail), stream(w2)
         xq = rms_norm(x, ln1.weight, ln1.eps) if sep else x
         if wide:
-            q = C.wide_qkv_rope_cache(xq, pq, ng, r, hd, cos, sin, pos, kc, vc,
-                                      ip.device_offset if graph else None, 0 if graph else s0,
-                                      sq, kvs)
+            q = C.wide_qkv_rope_cache(xq, pq, ng, r, hd, cos, sin, pos, kv.kc, kv.vc,
+                                      kv.slot_t, kv.slot, sq, kv.scales)
         else:
             q = C.skinny_qkv_rope_cache(xq, wq if pq is None else pq, None if sep else ln1.weight,
                                         ln1.eps, ng, r, hd,
-                                        cos, sin, pos, kc, vc,
-                                        ip.device_offset if graph else None, 0 if graph else s0,
-                                        pq is not None, sq, *(() if kvs is None else (kvs,)))
-        q4 = q.view(b, 1, ng * r, hd)
-        if table is not None:
-            o = flash_decode_cached(q4, kmem.transpose(0, 1), vmem.transpose(0, 1),
-                                    ip.device_kv_len, window=sa._window(ip.max_sequence_len),
-                                    kv_scale=kvs, page_table=table, capacity=ip.max_sequence_len)
-        elif graph:
-            o = flash_decode_cached(q4, kc.transpose(0, 1), vc.transpose(0, 1), ip.device_kv_len,
-                                    window=sa._window(kc.shape[0]), kv_scale=kvs)
-        elif kvs is not None:
-            # FP8 cache: every step reads the bytes in the FP8 decode kernel
-            # (the MHA route to the FlashAttention forward takes 16-bit K / V)
-            o = flash_decode_cached(q4, kc[:s0 + 1].transpose(0, 1), vc[:s0 + 1].transpose(0, 1),
-                                    None, window=sa._window(s0 + 1), kv_scale=kvs)
-        else:
-            o = flash_attn_func(q4, kc[:s0 + 1].transpose(0, 1), vc[:s0 + 1].transpose(0, 1),
-                                causal=True, window=sa._window(s0 + 1))
+                                        cos, sin, pos, kv.kc, kv.vc, kv.slot_t, kv.slot,
+                                        pq is not None, sq,
+                                        *(() if kv.scales is None else (kv.scales,)))
+        o = kv.decode(q.view(b, 1, ng * r, hd), sa._window)
         # Row-parallel dense / fc2 under TP: each rank's product is a partial
         # sum; TP rank 0 alone adds the residual in its epilogue, so one
         # all-reduce of [b, H] yields partial sums + residual (reference
