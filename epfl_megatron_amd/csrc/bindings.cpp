@@ -1212,6 +1212,128 @@ void flash_decode(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v,
   ema::flash_decode(p, dtype_code(q), cur_stream());
 }
 
+// ---------------------------------------------------------------- multi-row decode attention
+// q [b, sq, nq, hd] with 2 <= sq <= 16 (strides qs = (sb, ss, sg, sh)), k/v
+// caches as flash_decode takes them, out [b, sq, nq, hd] (strides (sb, ss, sh)).
+// The sq rows are already in the cache: kv_len counts them.
+void flash_decode_mq(const at::Tensor& q, const at::Tensor& k, const at::Tensor& v, at::Tensor out,
+                     int64_t b, int64_t sq, int64_t sk, int64_t nq, int64_t nkv, int64_t hd,
+                     std::vector<int64_t> qs, std::vector<int64_t> ks, std::vector<int64_t> vs,
+                     std::vector<int64_t> os, double scale, const c10::optional<at::Tensor>& kv_len,
+                     int64_t window, const c10::optional<at::Tensor>& kv_scale,
+                     const c10::optional<at::Tensor>& page_table) {
+  check_gpu(q, "q");
+  TORCH_CHECK(sq >= 2 && sq <= 16, "multi-row decode attention takes 2..16 query rows per sequence");
+  TORCH_CHECK(window >= 0, "sliding window must be >= 0 (0: none)");
+  TORCH_CHECK(qs.size() == 4 && ks.size() == 3 && vs.size() == 3 && os.size() == 3, "stride lists");
+  int64_t pt_ld = 0, n_pages = 0;
+  if (page_table) {
+    TORCH_CHECK(page_table->scalar_type() == at::kInt, "page_table must be an int32 tensor");
+    TORCH_CHECK(page_table->is_cuda() && page_table->device() == q.device(),
+                "page_table must be on q's device");
+    TORCH_CHECK(page_table->dim() == 2 && page_table->is_contiguous() && page_table->size(0) >= b &&
+                page_table->size(1) >= 1, "page_table must be 2-D contiguous [>= b, pages_per_row]");
+    pt_ld = page_table->size(1);
+    TORCH_CHECK(sk <= pt_ld * ema::KV_PAGE, "sk exceeds the page_table's ", pt_ld, " pages of ",
+                ema::KV_PAGE, " keys per row");
+    TORCH_CHECK(kv_len.has_value(), "a page_table needs kv_len (the keys each row's pages hold)");
+  }
+  const bool kv8 = k.scalar_type() == at::kByte || v.scalar_type() == at::kByte;
+  TORCH_CHECK(k.scalar_type() == v.scalar_type(), "k / v cache dtypes differ");
+  TORCH_CHECK(kv8 == kv_scale.has_value(), kv8 ? "an FP8 (uint8) cache needs its kv_scale tensor"
+                                               : "kv_scale given for a 16-bit cache");
+  const auto cache_t = kv8 ? at::kByte : q.scalar_type();
+  if (kv_len) {
+    TORCH_CHECK(kv_len->is_cuda() && kv_len->scalar_type() == at::kInt && kv_len->numel() >= 1,
+                "kv_len must be a device int32 tensor");
+    TORCH_CHECK(kv_len->device() == q.device(), "kv_len on another device");
+  }
+  TORCH_CHECK(k.scalar_type() == cache_t && v.scalar_type() == cache_t &&
+              out.scalar_type() == q.scalar_type(), "q/k/v/out dtype mismatch");
+  TORCH_CHECK(k.is_cuda() && v.is_cuda() && out.is_cuda() && k.device() == q.device() &&
+              v.device() == q.device() && out.device() == q.device(), "k / v / out on another device");
+  TORCH_CHECK(ema::flash_attn_supported((int)hd, dtype_code(q)), "decode attention supports "
+              "bf16/fp16 with head_dim 64 or 128");
+  TORCH_CHECK(nkv > 0 && nq % nkv == 0 && b > 0 && b < 65536 && sk > 0 && sk < (1ll << 30),
+              "bad decode shape");
+  TORCH_CHECK(q.dim() == 4 && q.size(0) == b && q.size(1) == sq && q.size(2) == nq && q.size(3) == hd &&
+              out.dim() == 4 && out.size(0) == b && out.size(1) == sq && out.size(2) == nq &&
+              out.size(3) == hd, "q / out must be [b, sq, nq, hd]");
+  TORCH_CHECK(q.stride(-1) == 1 && k.stride(-1) == 1 && v.stride(-1) == 1 && out.stride(-1) == 1,
+              "head_dim must be contiguous");
+  // a K / V piece is one 16-byte (FP8: 8-byte) load
+  for (int64_t s : ks) TORCH_CHECK(s % 8 == 0, "k strides must keep 16-byte alignment");
+  for (int64_t s : vs) TORCH_CHECK(s % 8 == 0, "v strides must keep 16-byte alignment");
+  for (int64_t s : qs) TORCH_CHECK(s % 8 == 0, "q strides must keep 16-byte alignment");
+  TORCH_CHECK(qs[0] == q.stride(0) && qs[1] == q.stride(1) && qs[3] == q.stride(2) &&
+              qs[2] == (nq / nkv) * qs[3], "q strides do not describe q");
+  TORCH_CHECK(os[0] == out.stride(0) && os[1] == out.stride(1) && os[2] == out.stride(2),
+              "out strides do not describe out");
+  for (const at::Tensor* t : {&q, &k, &v}) check_vec_aligned(*t, "q/k/v");
+  auto span = [](int64_t b, int64_t s, int64_t n, int64_t sb, int64_t ss, int64_t sn, int64_t hd) {
+    return (b - 1) * sb + (s - 1) * ss + (n - 1) * sn + hd;
+  };
+  int64_t span_b = b, span_s = sk;
+  if (page_table) {
+    TORCH_CHECK(k.dim() == 4 && v.dim() == 4 && k.size(0) == 1 && v.size(0) == 1 &&
+                k.size(1) == v.size(1), "paged k / v must be pool views [1, rows, nkv, hd]");
+    n_pages = k.size(1) / ema::KV_PAGE;
+    TORCH_CHECK(n_pages >= 1 && k.size(1) == n_pages * ema::KV_PAGE && k.size(1) < (1ll << 31),
+                "the k / v pool must hold n_pages * ", ema::KV_PAGE, " rows");
+    span_b = 1;
+    span_s = n_pages * ema::KV_PAGE;
+  }
+  for (int64_t s : ks) TORCH_CHECK(s >= 0, "k strides must not be negative");
+  for (int64_t s : vs) TORCH_CHECK(s >= 0, "v strides must not be negative");
+  TORCH_CHECK(k.storage_offset() + span(span_b, span_s, nkv, ks[0], ks[1], ks[2], hd) <=
+              (int64_t)(k.storage().nbytes() / k.element_size()), "k strides exceed storage");
+  TORCH_CHECK(v.storage_offset() + span(span_b, span_s, nkv, vs[0], vs[1], vs[2], hd) <=
+              (int64_t)(v.storage().nbytes() / v.element_size()), "v strides exceed storage");
+  ema::DecodeMqParams p{};
+  p.q = q.data_ptr(); p.k = k.data_ptr(); p.v = v.data_ptr(); p.o = out.data_ptr();
+  p.b = (int)b; p.sq = (int)sq; p.sk = (int)sk; p.nq = (int)nq; p.nkv = (int)nkv; p.hd = (int)hd;
+  p.q_sb = qs[0]; p.q_ss = qs[1]; p.q_sg = qs[2]; p.q_sh = qs[3];
+  p.k_sb = ks[0]; p.k_ss = ks[1]; p.k_sg = ks[2];
+  p.v_sb = vs[0]; p.v_ss = vs[1]; p.v_sg = vs[2];
+  p.o_sb = os[0]; p.o_ss = os[1]; p.o_sh = os[2];
+  p.scale = (float)scale;
+  if (kv_len) {
+    // one length per sequence when there is one element per row
+    p.kv_len_sb = (b > 1 && kv_len->numel() == b && kv_len->is_contiguous()) ? 1 : 0;
+    TORCH_CHECK(p.kv_len_sb == 1 || kv_len->numel() == 1 || b == 1,
+                "kv_len must hold one value or one per sequence");
+    p.kv_len = kv_len->data_ptr<int>();
+  }
+  if (page_table) {
+    p.page_table = page_table->data_ptr<int>();
+    p.pt_ld = (int)pt_ld;
+    p.n_pages = (int)n_pages;
+  }
+  if (kv8) {
+    p.kv_fp8 = 1;
+    p.k_scale = kv_scale_ptr(*kv_scale, nkv, q);
+    p.v_scale = p.k_scale + nkv;
+  }
+  p.window = window >= sk ? 0 : (int)window;  // sk bounds the valid keys
+  p.hps = ema::flash_decode_mq_heads((int)sq, (int)nq, (int)nkv);
+  p.chunk = ema::flash_decode_mq_chunk((int)b, (int)sq, (int)sk, (int)nq, (int)nkv);
+  const int64_t ns = ema::flash_decode_mq_splits((int)sk, p.chunk);
+  auto ws = at::empty({ema::flash_decode_mq_workspace((int)b, (int)sq, (int)nq, (int)ns, (int)hd)},
+                      q.options().dtype(at::kFloat));
+  p.ws_o = ws.data_ptr<float>();
+  p.ws_ml = p.ws_o + b * nq * sq * ns * hd;
+  // arrival counters of this kernel alone (a captured step keeps its pointer:
+  // the eager warm-up before capture sizes the buffer)
+  static std::vector<at::Tensor> counters;
+  const int dev = q.get_device();
+  if ((int)counters.size() <= dev) counters.resize(dev + 1);
+  const int64_t nc = ema::flash_decode_mq_counters((int)b, (int)sq, (int)nq, (int)nkv);
+  if (!counters[dev].defined() || counters[dev].numel() < nc)
+    counters[dev] = at::zeros({std::max<int64_t>(nc, 4096)}, q.options().dtype(at::kInt));
+  p.counters = reinterpret_cast<unsigned*>(counters[dev].data_ptr<int>());
+  ema::flash_decode_mq(p, dtype_code(q), cur_stream());
+}
+
 // ---------------------------------------------------------------- greedy decode tail
 // logits [b, V] (a view: rows 16-B aligned, last dim contiguous); tokens /
 // pos int64 with b contiguous elements, history int64 [b, H] rows contiguous,
@@ -1756,6 +1878,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("b"), py::arg("sk"), py::arg("nq"), py::arg("nkv"), py::arg("hd"), py::arg("qs"),
         py::arg("ks"), py::arg("vs"), py::arg("os"), py::arg("scale"), py::arg("kv_len"),
         py::arg("kpw") = 0, py::arg("window") = 0, py::arg("kv_scale") = py::none(),
+        py::arg("page_table") = py::none());
+  m.def("flash_decode_mq", &flash_decode_mq, py::arg("q"), py::arg("k"), py::arg("v"),
+        py::arg("out"), py::arg("b"), py::arg("sq"), py::arg("sk"), py::arg("nq"), py::arg("nkv"),
+        py::arg("hd"), py::arg("qs"), py::arg("ks"), py::arg("vs"), py::arg("os"), py::arg("scale"),
+        py::arg("kv_len"), py::arg("window") = 0, py::arg("kv_scale") = py::none(),
         py::arg("page_table") = py::none());
   m.def("kv_store_fp8", &kv_store_fp8, py::arg("k"), py::arg("v"), py::arg("kcache"),
         py::arg("vcache"), py::arg("kv_scale"), py::arg("slot_t") = py::none(),

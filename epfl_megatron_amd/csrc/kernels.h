@@ -329,6 +329,46 @@ void ragged_tail(const void* logits, int64_t ld, int V, int b, int dt, bool samp
 int flash_decode_splits(int sk, int kpw);
 int flash_decode_counters(int b, int nq, int nkv);
 void flash_decode(const DecodeParams& p, int dt, hipStream_t s);
+
+// ---- flash_decode_mq.hip: 2-16 query tokens per sequence against a KV cache --------------------
+// q [b, sq, nq, hd] whose sq rows are already in the cache: with n = the
+// sequence's key count (kv_len, else sk), token t sees key j iff j < e = n -
+// (sq - 1 - t) and (window == 0 or j >= e - window); e <= 0 gives zeros.
+struct DecodeMqParams {
+  const void* q;  // token t, head j of group g at b*q_sb + t*q_ss + g*q_sg + (j % r)*q_sh
+  const void* k;  // key i of group g at b*k_sb + i*k_ss + g*k_sg (KV8: bytes)
+  const void* v;
+  void* o;  // token t, head `head` at b*o_sb + t*o_ss + head*o_sh
+  int b, sq, sk, nq, nkv, hd;
+  int64_t q_sb, q_ss, q_sg, q_sh;
+  int64_t k_sb, k_ss, k_sg;
+  int64_t v_sb, v_ss, v_sg;
+  int64_t o_sb, o_ss, o_sh;
+  float scale;
+  float* ws_o;   // fp32 [b][nq][sq][splits][hd] chunk partials
+  float* ws_ml;  // fp32 [b][nq][sq][splits][2] chunk (max, sum) in log2 units
+  const int* kv_len;  // device int32 (nullptr: sk keys), kv_len_sb 0: one value, 1: one per sequence
+  int kv_len_sb;
+  unsigned* counters;  // zeroed uint32 [flash_decode_mq_counters()], re-armed by the kernel
+  int chunk;           // keys per workgroup: 128 or 256 (flash_decode_mq_chunk picks)
+  int hps;             // query heads of a group per workgroup (flash_decode_mq_heads)
+  int window;          // 0: none
+  int kv_fp8;          // as DecodeParams
+  const float* k_scale;
+  const float* v_scale;
+  const int* page_table;  // as DecodeParams
+  int pt_ld, n_pages;
+};
+// heads of a KV group per workgroup: min(r, 32 / sq) (whole heads, <= 32 packed rows)
+int flash_decode_mq_heads(int sq, int nq, int nkv);
+// keys per workgroup: 256 when that grid covers the 256 CUs, else 128
+int flash_decode_mq_chunk(int b, int sq, int sk, int nq, int nkv);
+int flash_decode_mq_splits(int sk, int chunk);
+int flash_decode_mq_counters(int b, int sq, int nq, int nkv);
+// fp32 elements of ws_o + ws_ml (ws_ml = ws_o + b * nq * sq * splits * hd)
+int64_t flash_decode_mq_workspace(int b, int sq, int nq, int splits, int hd);
+void flash_decode_mq(const DecodeMqParams& p, int dt, hipStream_t s);
+
 void flash_attn_bwd(const AttnBwdParams& p, int dt, hipStream_t s);
 
 // ---- xgmi_allreduce.hip --------------------------------------------------------------------------

@@ -54,6 +54,10 @@ class InferenceParams:
         # [batch] elements each: one per row (inference/continuous.py)
         self.device_offset = None
         self.device_kv_len = None
+        # opt-in: a call with 2..16 new tokens per row while device_offset is set
+        # is a multi-row device step (device_offset: the slot of each row's first
+        # new token, device_kv_len: the key count after them), not a prefill
+        self.device_multi = False
         # FP8 KV cache (--inference_fp8_kv_cache): per layer an fp32 device
         # tensor [2, nkv_per_tp] (row 0: K scales, row 1: V scales), 1.0 until
         # set; the kernels read it from device memory on every launch

@@ -13,6 +13,13 @@ The cells that exist, by ``step_kind`` (``LayerKV._check`` refuses the rest):
   ``ip.device_offset`` (one slot, or one per row) and ``flash_decode_cached``
   reads ``ip.device_kv_len`` keys of the whole cache.  Paged: one slot per row
   only (pool rows), read through the table.
+- device-slot multi-row step (opt-in: ``ip.device_multi``, with ``sq`` in 2..16
+  and ``ip.device_offset`` set): the ``sq`` new rows go to ``ip.device_offset +
+  t`` (the slot of each sequence's first new row, one value or one per row;
+  paged: physical, and the later rows through the table) and
+  ``flash_decode_cached`` reads ``ip.device_kv_len`` keys, the count after the
+  ``sq`` rows.  No host value is read.  Not with the fused decode layer, not
+  with FP8 calibration.
 - eager decode step: host slot ``s0``.  Not paged.
 - restart prefill: host slot 0; attends over the fresh K / V (16-bit columns:
   over the cached rows).  Paged: one row, scattered by its table.
@@ -56,12 +63,17 @@ DEVICE_DECODE = "device-slot decode"
 EAGER_DECODE = "eager decode"
 RESTART_PREFILL = "restart prefill"
 CONTINUED_PREFILL = "continued prefill"
+DEVICE_MULTI = "device-slot multi-row step"
 
 
 def step_kind(ip, sq):
-    """Which of the four steps a call with ``sq`` new tokens per row is."""
+    """Which of the steps a call with ``sq`` new tokens per row is (the
+    multi-row device step only under ``ip.device_multi``: the graphed decoders
+    keep ``device_offset`` set while their prefills run)."""
     if sq == 1:
         return EAGER_DECODE if ip.device_offset is None else DEVICE_DECODE
+    if ip.device_offset is not None and getattr(ip, "device_multi", False):
+        return DEVICE_MULTI
     return RESTART_PREFILL if ip.sequence_len_offset == 0 else CONTINUED_PREFILL
 
 
@@ -105,7 +117,7 @@ class LayerKV:
             self.kc, self.vc = kmem, vmem
         else:
             self.kc, self.vc = kmem[:, b0:b0 + b], vmem[:, b0:b0 + b]
-        if kind == DEVICE_DECODE:
+        if kind in (DEVICE_DECODE, DEVICE_MULTI):
             self.slot_t, self.slot = ip.device_offset, 0
         else:
             self.slot_t, self.slot = None, s0
@@ -116,6 +128,22 @@ class LayerKV:
         if kind == DEVICE_DECODE and on_gpu and not self.native:
             raise NotImplementedError("hipGraph decode needs the native decode attention "
                                       "kernel (GPU, bf16/fp16, head_dim 64 or 128)")
+        if kind == DEVICE_MULTI:
+            if fused:
+                raise NotImplementedError("the fused decode layer is single-row: a multi-row "
+                                          "device step (device_multi) runs the unfused layer")
+            if self.fp8 and FP8_KV_CALIBRATE:
+                raise NotImplementedError("a multi-row device step does not calibrate the FP8 KV "
+                                          "scales (--inference_fp8_kv_calibrate)")
+            if sq > 16:
+                raise NotImplementedError("a multi-row device step takes 2..16 rows per sequence")
+            if ip.device_offset.numel() not in (1, b):
+                raise NotImplementedError("a multi-row device step needs one device cache slot, "
+                                          "or one per row")
+            if self.paged and ip.device_offset.numel() != b:
+                raise NotImplementedError("paged KV cache: a multi-row device step needs one "
+                                          "device cache slot per row")
+            return
         if not self.paged:
             return
         why = None
@@ -145,6 +173,8 @@ class LayerKV:
         s0, sc, kc, vc, kmem, vmem = self.s0, self.scales, self.kc, self.vc, self.kmem, self.vmem
         sq, b = k.shape[:2]
         slots = self.slot_t
+        if self.kind == DEVICE_MULTI:
+            return self._write_multi(k, v)
         if self.paged:
             # the FP8 pool's HIP store kernel, else fp8_kv.quantize and torch indexing
             store8 = self.fp8 and fp8_kv.store_native_ok(k) and fp8_kv.store_native_ok(v)
@@ -188,6 +218,31 @@ class LayerKV:
             kc.index_copy_(0, slots, k)
             vc.index_copy_(0, slots, v)
 
+    def _write_multi(self, k, v):
+        """The ``sq`` rows of a multi-row device step: row ``t`` of sequence ``m``
+        to slot ``device_offset[m] + t``, all indices on the device."""
+        sc, kmem, vmem = self.scales, self.kmem, self.vmem
+        sq, b = k.shape[:2]
+        first = self.slot_t.reshape(-1).long()
+        steps = torch.arange(sq, device=k.device)
+        if self.fp8:
+            k, v = fp8_kv.quantize(k, sc[0]), fp8_kv.quantize(v, sc[1])
+        if self.paged:
+            # the first slot is physical; the rows after it may cross into the
+            # sequence's next page: their logical positions through the table
+            pos = (self.ip.device_kv_len.reshape(-1).long().expand(b) - sq)[None, :] + steps[:, None]
+            pi = (pos // KV_PAGE).clamp(0, self.table.shape[1] - 1)
+            page = self.table.long().gather(1, pi.t()).t()
+            idx = page * KV_PAGE + pos % KV_PAGE
+            idx = torch.cat([first[None, :], idx[1:]], 0).reshape(-1)
+            kmem.index_copy_(0, idx, k.reshape(sq * b, 1, *k.shape[2:]))
+            vmem.index_copy_(0, idx, v.reshape(sq * b, 1, *v.shape[2:]))
+            return
+        rows = first[None, :] + steps[:, None]  # [sq, b] (one slot for the batch broadcasts)
+        cols = torch.arange(self.b0, self.b0 + b, device=k.device)[None, :]
+        kmem[rows, cols] = k
+        vmem[rows, cols] = v
+
     def decode(self, q, window):
         """Attention of one query row per sequence, ``q [b, 1, np, hd]`` -> ``[b,
         1, np, hd]``, over the cache with the new row in it: the device-slot
@@ -222,7 +277,18 @@ class LayerKV:
         n = s0 + sq
         qt = q.transpose(0, 1)
         fp8_native = self.fp8 and self.native and flash
-        if self.kind == DEVICE_DECODE or (sq == 1 and fp8_native):
+        if self.kind == DEVICE_MULTI:
+            ip = self.ip
+            if self.paged:
+                o = flash_decode_cached(qt, self.kmem.transpose(0, 1), self.vmem.transpose(0, 1),
+                                        ip.device_kv_len, window=window(ip.max_sequence_len),
+                                        kv_scale=sc, page_table=self.table,
+                                        capacity=ip.max_sequence_len)
+            else:
+                o = flash_decode_cached(qt, self.kc.transpose(0, 1), self.vc.transpose(0, 1),
+                                        ip.device_kv_len, window=window(self.kc.shape[0]),
+                                        kv_scale=sc)
+        elif self.kind == DEVICE_DECODE or (sq == 1 and fp8_native):
             o = self.decode(qt, window)
         elif self.paged and s0 > 0 and flash:  # continued: the first s0 keys are in the pages only
             o = flash_attn_paged(qt, self.kmem.transpose(0, 1), self.vmem.transpose(0, 1),

@@ -174,9 +174,57 @@ def _flash_decode(q, k, v, scale, kv_len=None, window=0, kv_scale=None, page_tab
     return out
 
 
+def _decode_cached_mq(q, k, v, kv_len, softmax_scale, window, kv_scale, page_table, capacity):
+    """``flash_decode_cached`` for 2..16 query rows per sequence (its mask)."""
+    b, sq, nq, d = q.shape
+    nkv = k.shape[2]
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(d)
+    if page_table is not None:
+        from ..inference.paged import KV_PAGE, gather_rows
+        if kv_len is None:
+            raise ValueError("a page_table needs kv_len (the keys each row's pages hold)")
+        if capacity is None:
+            capacity = page_table.shape[1] * KV_PAGE
+        if capacity > page_table.shape[1] * KV_PAGE:
+            raise ValueError("capacity exceeds the page_table's pages per row")
+    else:
+        capacity = k.shape[1]
+    if use_native(q) and d in (64, 128) and q.dtype in (torch.bfloat16, torch.float16):
+        out = torch.empty(b, sq, nq, d, dtype=q.dtype, device=q.device)
+        ext().flash_decode_mq(q, k, v, out, b, sq, int(capacity), nq, nkv, d,
+                              list(_bsnd_strides(q, nq // nkv)), list(_bsnd_strides(k, 1)[:3]),
+                              list(_bsnd_strides(v, 1)[:3]),
+                              [out.stride(0), out.stride(1), out.stride(2)], float(scale), kv_len,
+                              window=int(window), kv_scale=kv_scale, page_table=page_table)
+        return out
+    # per sequence: gather (and dequantise) its keys, mask, reference attention
+    lens = kv_len.reshape(-1).tolist() if kv_len is not None else [capacity]
+    lens = lens * b if len(lens) == 1 else lens
+    out = torch.zeros_like(q)
+    for i in range(b):
+        n = min(lens[i], capacity)
+        if n <= 0:
+            continue
+        if page_table is not None:
+            ki, vi = (gather_rows(t[0], page_table[i], n)[None] for t in (k, v))
+        else:
+            ki, vi = k[i:i + 1, :n], v[i:i + 1, :n]
+        if kv_scale is not None:
+            from . import fp8_kv
+            ki = fp8_kv.dequantize(ki, kv_scale[0], q.dtype)
+            vi = fp8_kv.dequantize(vi, kv_scale[1], q.dtype)
+        for t in range(sq):
+            e = n - (sq - 1 - t)
+            if e <= 0:
+                continue
+            lo = max(e - window, 0) if window else 0
+            out[i, t] = attention_ref(q[i:i + 1, t:t + 1], ki[:, lo:e], vi[:, lo:e], False, scale)[0, 0]
+    return out
+
+
 def flash_decode_cached(q, k, v, kv_len, softmax_scale=None, window=0, kv_scale=None,
                         page_table=None, capacity=None):
-    """One query row per sequence against a whole KV cache ``k / v [b, smax,
+    """One query row per sequence (or 2..16, below) against a whole KV cache ``k / v [b, smax,
     nkv, d]`` of which the first ``kv_len`` (device int32) keys are valid
     (with ``window``: the last ``window`` of those).  ``kv_len`` None: all
     ``smax`` keys are valid.  ``kv_scale``: fp32 ``[2, nkv]`` when k / v are an
@@ -189,8 +237,22 @@ def flash_decode_cached(q, k, v, kv_len, softmax_scale=None, window=0, kv_scale=
     nkv, d]``, key ``j`` of row ``i`` is pool row ``page_table[i, j // KV_PAGE] *
     KV_PAGE + j % KV_PAGE``, ``kv_len`` is required and ``capacity`` (default
     ``pages_per_row * KV_PAGE``) is the logical cache length that sizes the
-    launch as ``smax`` does without a table."""
+    launch as ``smax`` does without a table.
+
+    ``q.shape[1] = sq`` in 2..16: a multi-row step (``csrc/flash_decode_mq.hip``).
+    The ``sq`` new rows are already in the cache and ``kv_len`` counts them:
+    with ``n_i`` keys in row ``i`` and ``e = n_i - (sq - 1 - t)``, query token
+    ``t`` sees key ``j`` iff ``j < e`` and (``window == 0`` or ``j >= e -
+    window``); a token with ``e <= 0`` gives zeros.  More rows than 16 are a
+    prefill: ``flash_attn_func`` / ``flash_attn_paged``."""
     _check_window(window, True)
+    sq = q.shape[1]
+    if sq > 16:
+        raise ValueError(f"flash_decode_cached takes 1..16 query rows per sequence, got {sq}: "
+                         "use flash_attn_func (flash_attn_paged on a pool) for a prefill")
+    if sq > 1:
+        return _decode_cached_mq(q, k, v, kv_len, softmax_scale, window, kv_scale, page_table,
+                                 capacity)
     if page_table is not None:
         from ..inference.paged import KV_PAGE, gather_rows
         if kv_len is None:
