@@ -1457,6 +1457,50 @@ void ragged_tail(const at::Tensor& logits, at::Tensor tokens, at::Tensor history
                    ctl.data_ptr<int64_t>(), fctl.data_ptr<float>(), cur_stream());
 }
 
+// Speculative tail (inference/speculative.py): logits [b * S, V] of a step with
+// S = tokens.size(1) rows per sequence; tokens / pos int64 [b, S], slot /
+// hist_len / limit / accepted int64 [b], kv_len / active int32 [b], history
+// int64 [b, H], tick int64 [1], ctl int64 [3] = [stop_id, ngram, still active
+// (written)], am int32 [b, S] (scratch), counters int32 [b + 1] (zeroed once).
+void spec_tail(const at::Tensor& logits, at::Tensor tokens, at::Tensor pos, at::Tensor slot,
+               at::Tensor kv_len, at::Tensor history, at::Tensor hist_len, at::Tensor limit,
+               at::Tensor active, at::Tensor accepted, at::Tensor tick, at::Tensor ctl,
+               at::Tensor am, at::Tensor counters) {
+  const int dt = check_sample_logits(logits, "spec_tail");
+  const auto dev = logits.device();
+  TORCH_CHECK(tokens.dim() == 2, "spec_tail: tokens [b, S]");
+  const int64_t b = tokens.size(0), S = tokens.size(1), V = logits.size(1);
+  TORCH_CHECK(S >= 2 && S <= 16 && b >= 1 && logits.size(0) == b * S && b * S < 65536,
+              "spec_tail: S in 2..16, logits [b * S, V], b * S < 65536");
+  for (const at::Tensor* t : {&tokens, &pos})
+    TORCH_CHECK(t->device() == dev && t->scalar_type() == at::kLong && t->is_contiguous() &&
+                    t->dim() == 2 && t->size(0) == b && t->size(1) == S,
+                "spec_tail: tokens / pos int64 [b, S]");
+  for (const at::Tensor* t : {&slot, &hist_len, &limit, &accepted})
+    TORCH_CHECK(t->device() == dev && t->scalar_type() == at::kLong && t->is_contiguous() &&
+                    t->numel() == b, "spec_tail: int64 [b] state tensors");
+  for (const at::Tensor* t : {&kv_len, &active})
+    TORCH_CHECK(t->device() == dev && t->scalar_type() == at::kInt && t->is_contiguous() &&
+                    t->numel() == b, "spec_tail: kv_len / active int32 [b]");
+  TORCH_CHECK(history.device() == dev && history.scalar_type() == at::kLong && history.dim() == 2 &&
+                  history.size(0) == b && history.stride(1) == 1 && history.size(1) >= 1 &&
+                  history.size(1) < (1ll << 31), "spec_tail: history int64 [b, H]");
+  TORCH_CHECK(tick.device() == dev && tick.scalar_type() == at::kLong && tick.numel() == 1 &&
+                  ctl.device() == dev && ctl.scalar_type() == at::kLong && ctl.is_contiguous() &&
+                  ctl.numel() == 3, "spec_tail: tick int64 [1], ctl int64 [3]");
+  TORCH_CHECK(am.device() == dev && am.scalar_type() == at::kInt && am.is_contiguous() &&
+                  am.numel() == b * S && counters.device() == dev &&
+                  counters.scalar_type() == at::kInt && counters.is_contiguous() &&
+                  counters.numel() == b + 1, "spec_tail: am int32 [b, S], counters int32 [b + 1]");
+  ema::SpecTail st{(int)b, tokens.data_ptr<int64_t>(), pos.data_ptr<int64_t>(),
+                   slot.data_ptr<int64_t>(), kv_len.data_ptr<int>(), history.data_ptr<int64_t>(),
+                   history.stride(0), (int)history.size(1), hist_len.data_ptr<int64_t>(),
+                   limit.data_ptr<int64_t>(), active.data_ptr<int>(), accepted.data_ptr<int64_t>(),
+                   tick.data_ptr<int64_t>(), ctl.data_ptr<int64_t>(), am.data_ptr<int>(),
+                   reinterpret_cast<unsigned*>(counters.data_ptr<int>())};
+  ema::spec_tail(logits.data_ptr(), logits.stride(0), (int)V, (int)S, dt, st, cur_stream());
+}
+
 // One draw per row of logits [b, V] into tokens int64 [b]; no tail state, the
 // settings are launch arguments (noise offset = offset, step 0).
 void sample_rows(const at::Tensor& logits, at::Tensor tokens, int64_t seed, int64_t offset,
@@ -1854,6 +1898,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("hist_idx"), py::arg("pos"), py::arg("slot"), py::arg("kv_len"), py::arg("active"),
         py::arg("limit"), py::arg("tick"), py::arg("counter"), py::arg("ctl"), py::arg("fctl"),
         py::arg("sample") = false, py::arg("page_table") = py::none(), py::arg("n_pages") = 0);
+  m.def("spec_tail", &spec_tail, py::arg("logits"), py::arg("tokens"), py::arg("pos"),
+        py::arg("slot"), py::arg("kv_len"), py::arg("history"), py::arg("hist_len"),
+        py::arg("limit"), py::arg("active"), py::arg("accepted"), py::arg("tick"), py::arg("ctl"),
+        py::arg("am"), py::arg("counters"));
   m.attr("KV_PAGE") = (int)ema::KV_PAGE;
   m.def("sample_rows", &sample_rows, py::arg("logits"), py::arg("tokens"), py::arg("seed"),
         py::arg("offset"), py::arg("top_k"), py::arg("top_p"), py::arg("temperature"),

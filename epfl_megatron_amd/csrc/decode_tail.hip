@@ -12,6 +12,9 @@
 // active flag per row, so a finished row parks and can be refilled between
 // replays of the same graph.  The selection code (argmax_row, draw_row) is
 // shared; only thread 0's bookkeeping differs.
+// spec_tail_k (inference/speculative.py) is the tail of a speculative greedy
+// step: S logits rows per sequence, one workgroup each, and the last of a
+// sequence's workgroups to arrive verifies the drafts, commits and drafts anew.
 //
 // Reference: megatron/text_generation/generation.py:179-264 samples on the
 // host-driven loop (greedy = argmax of the last position's logits).
@@ -503,7 +506,164 @@ __global__ __launch_bounds__(1024) void ragged_tail_k(const T* __restrict__ logi
   }
 }
 
+// ---------------------------------------------------------------- speculative tail
+// spec_tail_k (inference/speculative.py): the tail of one speculative greedy
+// step of b sequences with S rows each (S in 2..16, D = S - 1 drafts).  Row 0
+// of a sequence carries its last committed token, rows 1..D the drafts; the
+// forward ran all S through the multi-row device step, so logits row r * S + t
+// is the model's answer after draft t.  State per sequence r (SpecTail), with p
+// = hist_len[r] - 1: tokens[r, :], pos[r, t] = p + t, slot[r] = p, kv_len[r] =
+// p + S, history[r, :hist_len[r]] = the whole context by position.
+//
+// Grid: b * S workgroups of 1024 threads, those of a sequence adjacent.
+// Workgroup (r, t) takes argmax_row of its logits row, stores it in am[r, t]
+// (write-through, agent scope, drained before the arrival is counted: the
+// protocol of decode_attn_k's combine) and arrives at counters[r].  Nobody
+// waits: the last of the S to arrive acquires am[r, :] and does the
+// sequence's bookkeeping with all its threads (the flag goes through LDS):
+//   accept n   = leading t in 0..D-1 with tokens[r, t + 1] == a[t];
+//   commit     a[0..n], cut to max(limit - hist_len, 1) tokens and after the
+//              first stop_id: c >= 1 tokens appended to history, hist_len += c,
+//              accepted += c - 1;
+//   park       if it ended on stop_id or hist_len reached limit: active = 0,
+//              tokens / pos / slot / kv_len stay (the row rewrites its S slots);
+//   else       pos / slot / kv_len follow the new p, tokens[r, 0] = the last
+//              committed token and tokens[r, 1..D] = the n-gram draft.
+// Draft: for g = ngram (ctl[1], 0..4) down to 1, the largest start j <
+// hist_len - g with history[j .. j + g) == the last g tokens; the first g with
+// a match wins and draft k = history[j + g + k] where that is < hist_len, else
+// the last committed token (as every draft without a match).  One pass serves
+// every g: a candidate is its end e = j + g in [1, hist_len), m(e) = how many
+// tokens before e agree with the tokens before hist_len (up to 4), and g's
+// winner is the largest e with m(e) >= g: four max-reductions, side by side.
+// An inactive sequence reads no logits and writes nothing.  Every workgroup
+// then arrives at counters[b], the finisher of a sequence that goes on with
+// 1 << 16 on top; the last one advances *tick, writes the number of sequences
+// still active to ctl[2] and re-arms (each sequence's finisher re-armed its own).
+constexpr int SPEC_MAX_G = 4;
+
+template <typename T>
+__global__ __launch_bounds__(1024) void spec_tail_k(const T* __restrict__ logits, int64_t ld, int V,
+                                                   int S, SpecTail st) {
+  const int r = blockIdx.x / S, t = blockIdx.x % S, tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  __shared__ int last_sh, hl_sh, a_sh[16], best_sh[1024 / 64][SPEC_MAX_G];
+  __shared__ int64_t tok_sh[16], suf_sh[SPEC_MAX_G];
+  unsigned still = 0u;
+  bool finisher = false;
+  if (st.active[r] != 0) {  // (the finisher alone writes it, after all S have read it)
+    const int bi = argmax_row<T>(logits + ((int64_t)r * S + t) * ld, V, tid);
+    if (tid == 0) {
+      __hip_atomic_store(st.am + r * S + t, bi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const unsigned prev = __hip_atomic_fetch_add(st.counters + r, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const int last = prev == (unsigned)S - 1u;
+      if (last) {
+        __hip_atomic_store(st.counters + r, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      }
+      last_sh = last;
+    }
+    __syncthreads();
+    finisher = last_sh != 0;
+  }
+  if (finisher) {
+    const int D = S - 1;
+    int64_t* hist = st.history + (int64_t)r * st.hist_ld;
+    if (tid < S) {
+      a_sh[tid] = __hip_atomic_load(st.am + r * S + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      tok_sh[tid] = st.tokens[r * S + tid];
+      // read before the barrier: thread 0 stores the new hist_len behind it
+      if (tid == 0) hl_sh = (int)st.hist_len[r];
+    }
+    __syncthreads();
+    const int64_t stop_id = st.ctl[0];
+    const int G = (int)min(max(st.ctl[1], (int64_t)0), (int64_t)SPEC_MAX_G);
+    const int hl = hl_sh;
+    int n = 0;
+    while (n < D && tok_sh[n + 1] == (int64_t)a_sh[n]) ++n;
+    int c = min(n + 1, max((int)(st.limit[r] - hl), 1));
+    bool stopped = false;
+    if (stop_id >= 0) {
+      for (int i = 0; i < c; ++i) {
+        if ((int64_t)a_sh[i] == stop_id) {
+          c = i + 1;
+          stopped = true;
+          break;
+        }
+      }
+    }
+    const int nl = hl + c;  // the new hist_len
+    if (tid < c && hl + tid >= 0 && hl + tid < st.hist_cols) hist[hl + tid] = a_sh[tid];
+    // the context by position, the tokens just committed included (from LDS:
+    // no thread reads what another one has just stored)
+    auto h = [&](int i) -> int64_t {
+      return i >= hl ? (int64_t)a_sh[i - hl] : i < st.hist_cols ? hist[i] : (int64_t)-1;
+    };
+    const bool go = !stopped && nl < st.limit[r];
+    if (tid == 0) {
+      st.hist_len[r] = nl;
+      st.accepted[r] += c - 1;
+      if (!go) st.active[r] = 0;
+    }
+    if (go) {
+      still = 1u;
+      if (tid < SPEC_MAX_G) suf_sh[tid] = nl - 1 - tid >= 0 ? h(nl - 1 - tid) : (int64_t)-1;
+      __syncthreads();
+      int best[SPEC_MAX_G];
+#pragma unroll
+      for (int g = 0; g < SPEC_MAX_G; ++g) best[g] = -1;
+      if (G > 0) {
+        for (int e = 1 + tid; e < nl; e += 1024) {  // ascending: a later match replaces an earlier
+          int m = 0;
+          while (m < G && m < e && h(e - 1 - m) == suf_sh[m]) ++m;
+#pragma unroll
+          for (int g = 0; g < SPEC_MAX_G; ++g)
+            if (m > g) best[g] = e;
+        }
+      }
+#pragma unroll
+      for (int g = 0; g < SPEC_MAX_G; ++g) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) best[g] = max(best[g], __shfl_xor(best[g], o, 64));
+        if (lane == 0) best_sh[wave][g] = best[g];
+      }
+      __syncthreads();
+      if (tid < S) {
+        int e = -1;  // one past the winning match
+        for (int g = G - 1; g >= 0 && e < 0; --g)
+          for (int w = 0; w < 1024 / 64; ++w) e = max(e, best_sh[w][g]);
+        const int64_t last_tok = a_sh[c - 1];
+        int64_t tok = last_tok;
+        if (tid > 0 && e >= 0 && e + tid - 1 < nl) tok = h(e + tid - 1);
+        st.tokens[r * S + tid] = tok;
+        st.pos[r * S + tid] = nl - 1 + tid;
+        if (tid == 0) {
+          st.slot[r] = nl - 1;
+          st.kv_len[r] = nl - 1 + S;
+        }
+      }
+    }
+  }
+  if (tid != 0) return;
+  const unsigned prev = __hip_atomic_fetch_add(st.counters + st.b, 1u + (still << 16), __ATOMIC_RELAXED,
+                                               __HIP_MEMORY_SCOPE_AGENT);
+  if ((prev & 0xffffu) == gridDim.x - 1) {
+    *st.tick += 1;
+    st.ctl[2] = (int64_t)((prev >> 16) + still);
+    __hip_atomic_store(st.counters + st.b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
 }  // namespace
+
+void spec_tail(const void* logits, int64_t ld, int V, int S, int dt, const SpecTail& st, hipStream_t s) {
+  EMA_DISPATCH_FLOAT(dt, T, {
+    hipLaunchKernelGGL((spec_tail_k<T>), dim3((unsigned)(st.b * S)), dim3(1024), 0, s, (const T*)logits,
+                       ld, V, S, st);
+  });
+}
 
 void ragged_tail(const void* logits, int64_t ld, int V, int b, int dt, bool sample, int64_t* tokens,
                  int64_t* history, int64_t hist_ld, int64_t hist_cols, const RaggedTail& st,

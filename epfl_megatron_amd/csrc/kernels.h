@@ -326,6 +326,30 @@ struct RaggedTail {
 void ragged_tail(const void* logits, int64_t ld, int V, int b, int dt, bool sample, int64_t* tokens,
                  int64_t* history, int64_t hist_ld, int64_t hist_cols, const RaggedTail& st,
                  unsigned* counter, int64_t* ctl, const float* fctl, hipStream_t s);
+// Tail of one speculative greedy step (inference/speculative.py): b sequences
+// of S rows (2..16), logits [b * S, V]; b * S < 65536.  Semantics at
+// spec_tail_k in decode_tail.hip.  ctl int64 [3] = [stop_id, ngram (0..4), the
+// number of sequences still active (written)]; am int32 [b, S] is scratch;
+// counters uint32 [b + 1], zeroed once (one per sequence, then the grid's).
+struct SpecTail {
+  int b;
+  int64_t* tokens;  // [b, S]
+  int64_t* pos;     // [b, S]
+  int64_t* slot;    // [b]
+  int* kv_len;      // [b]
+  int64_t* history;  // [b, hist_cols], row stride hist_ld
+  int64_t hist_ld;
+  int hist_cols;
+  int64_t* hist_len;  // [b]
+  const int64_t* limit;
+  int* active;
+  int64_t* accepted;
+  int64_t* tick;  // [1]
+  int64_t* ctl;
+  int* am;
+  unsigned* counters;
+};
+void spec_tail(const void* logits, int64_t ld, int V, int S, int dt, const SpecTail& st, hipStream_t s);
 int flash_decode_splits(int sk, int kpw);
 int flash_decode_counters(int b, int nq, int nkv);
 void flash_decode(const DecodeParams& p, int dt, hipStream_t s);

@@ -19,7 +19,8 @@ The cells that exist, by ``step_kind`` (``LayerKV._check`` refuses the rest):
   paged: physical, and the later rows through the table) and
   ``flash_decode_cached`` reads ``ip.device_kv_len`` keys, the count after the
   ``sq`` rows.  No host value is read.  Not with the fused decode layer, not
-  with FP8 calibration.
+  with FP8 calibration.  Caller: ``SpeculativeGreedyDecoder``
+  (``inference/speculative.py``), whose verify step is this cell.
 - eager decode step: host slot ``s0``.  Not paged.
 - restart prefill: host slot 0; attends over the fresh K / V (16-bit columns:
   over the cached rows).  Paged: one row, scattered by its table.

@@ -40,7 +40,13 @@ without the cache.
 against GraphedGreedyDecoder from the same prefilled cache, --reps repetitions
 each, alternating; the spread of the lockstep decoder's repetitions is the margin.
 
-Usage: python scripts/serve_bench.py [--batches 1,8,32] [--graph]
+--graph --speculative S [--ngram G]: SpeculativeGreedyDecoder (inference/
+speculative.py: S rows per sequence, n-gram drafts verified in the captured
+graph) against GraphedGreedyDecoder from the same prefilled prompt, --reps
+repetitions each, alternating, once on a prompt of period 8 and once on a random
+one; reports tokens/s, ms per replay and the mean accepted drafts per step.
+
+Usage: python scripts/serve_bench.py [--batches 1,8,32] [--graph [--speculative S [--ngram G]]]
        [--top_k K | --top_p P] [--temperature T]
        [--continuous [--requests N] [--prompt_range LO,HI] [--gen_range LO,HI]
         [--poll_every 1,4,16] [--kv_pages N] [--capacity C]] [--ragged_cost [--reps 3]]
@@ -110,6 +116,9 @@ def main():
                     help="--prefix_share: prompt lengths LO,HI of the list without a common prefix")
     ap.add_argument("--prefill_chunk", type=int, default=0,
                     help="--prefix_share: ContinuousBatcher prefill_chunk (0: whole prompts)")
+    ap.add_argument("--speculative", type=int, default=0,
+                    help="--graph: rows per sequence of SpeculativeGreedyDecoder (2..16; 0: off)")
+    ap.add_argument("--ngram", type=int, default=3, help="--speculative: longest n-gram looked up")
     a = ap.parse_args()
     sampling = a.top_k > 0 or a.top_p > 0.0 or a.temperature != 1.0
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=os.environ.get("MASTER_PORT", "29561"),
@@ -158,6 +167,8 @@ def main():
         return continuous(a, m, sampling, skw)
     if a.ragged_cost:
         return ragged_cost(a, m)
+    if a.graph and a.speculative:
+        return speculative(a, m)
     res = []
     for B in [int(x) for x in a.batches.split(",")]:
         total = a.prompt + a.gen
@@ -425,6 +436,67 @@ def prefix_share(a, m):
                      baseline_prefilled_tokens=cbs["baseline"].prefilled_tokens,
                      evictions=cb.evictions, admission_waits=cb.waits,
                      same_tokens=outs["prefix_cache"] == outs["baseline"])
+            print(json.dumps(r), flush=True)
+            res.append(r)
+    return res
+
+
+def speculative(a, m):
+    """--graph --speculative S: tokens/s of the speculative and the lockstep
+    greedy decoder for --gen tokens after the same prompt, alternating."""
+    import torch
+    from epfl_megatron_amd.inference import SpeculativeGreedyDecoder
+    from epfl_megatron_amd.inference.forward_step import InferenceParams
+    from epfl_megatron_amd.inference.hip_graph import GraphedGreedyDecoder
+    S, res = a.speculative, []
+    total = a.prompt + a.gen + S
+    for B in [int(x) for x in a.batches.split(",")]:
+        g = torch.Generator().manual_seed(a.seed)
+        pos = torch.arange(a.prompt, device="cuda")[None].expand(B, -1)
+        prompts = {"repetitive": torch.randint(0, 32000, (B, 8), generator=g).repeat(1, a.prompt // 8 + 1),
+                   "random": torch.randint(0, 32000, (B, a.prompt + 8), generator=g)}
+        for kind, prompt in prompts.items():
+            prompt = prompt[:, :a.prompt].cuda()
+            decs, secs, replays = {}, {"greedy": [], "speculative": []}, 0
+            with torch.no_grad():
+                for name in secs:
+                    ip = InferenceParams(B, total)
+                    nxt = m(prompt, pos, None, inference_params=ip)[:, -1].argmax(-1)
+                    ip.sequence_len_offset = a.prompt
+                    decs[name] = GraphedGreedyDecoder(m, ip, B, a.gen) if name == "greedy" else \
+                        SpeculativeGreedyDecoder(m, ip, B, a.gen, rows=S, ngram=a.ngram)
+                for rep in range(a.reps + 1):  # rep 0: capture and warm-up
+                    for name, dec in decs.items():
+                        if name == "greedy":
+                            dec.start(nxt.view(B, 1), a.prompt)
+                        else:
+                            dec.start(prompt, nxt)
+
+                        def run():
+                            if name == "greedy":
+                                for _ in range(a.gen):
+                                    dec.step()
+                                return a.gen
+                            while dec.active_rows():  # one host read per 4 replays
+                                for _ in range(4):
+                                    dec.step()
+                            return int(dec.tick)
+                        n, dt = _timed(run)
+                        if rep:
+                            secs[name].append(round(dt, 4))
+                            replays = n if name == "speculative" else replays
+            spec = decs["speculative"]
+            toks, lens = spec.generated()
+            r = {"mode": "speculative", "batch": B, "rows": S, "ngram": a.ngram, "prompt_kind": kind,
+                 "prompt": a.prompt, "gen": a.gen, "mean_accepted": round(spec.mean_accepted(), 3),
+                 "speculative_replays": replays,
+                 "same_tokens": bool(lens.eq(a.gen).all()) and
+                 torch.equal(toks, decs["greedy"].history[:, :a.gen])}
+            for name, t in secs.items():
+                n = a.gen if name == "greedy" else replays
+                r[name + "_seconds"] = t
+                r[name + "_tokens_per_s"] = [round(B * a.gen / x, 1) for x in t]
+                r[name + "_ms_per_replay"] = [round(1e3 * x / n, 3) for x in t]
             print(json.dumps(r), flush=True)
             res.append(r)
     return res
