@@ -952,6 +952,92 @@ void kv_store_fp8(const at::Tensor& k, const at::Tensor& v, at::Tensor kcache, a
   ema::kv_store_fp8(p, dtype_code(k), cur_stream());
 }
 
+// Front of the device-slot multi-row step (csrc/kv_write_multi.hip): qkv5 [sq,
+// b, g, r + 2, hd] bf16 / fp16 is rotated in place (q and k heads; cos / sin
+// fp32 [max_pos, hd / 2] at pos int64 [b, sq]; none: no rotation) and its k / v
+// rows go to rows slot[m] + t of kcache / vcache [L, >= b, g, hd] (of qkv5's
+// dtype, or uint8 e4m3 with kv_scale fp32 [2, g]); slot int64 with 1 or b
+// elements.  page_table int32 [>= b, pages]: the caches are the pool as a
+// stride-0 batch view, and rows t >= 1 go through the table at kv_len - sq + t
+// (kv_len int32, 1 or b elements).
+void kv_write_multi(at::Tensor qkv5, const c10::optional<at::Tensor>& cos,
+                    const c10::optional<at::Tensor>& sin, const c10::optional<at::Tensor>& pos,
+                    at::Tensor kcache, at::Tensor vcache, const at::Tensor& slot,
+                    const c10::optional<at::Tensor>& kv_len,
+                    const c10::optional<at::Tensor>& kv_scale,
+                    const c10::optional<at::Tensor>& page_table) {
+  check_gpu(qkv5, "qkv");
+  const auto dev = qkv5.device();
+  TORCH_CHECK(qkv5.scalar_type() == at::kBFloat16 || qkv5.scalar_type() == at::kHalf,
+              "kv_write_multi: qkv must be bf16 or fp16");
+  TORCH_CHECK(qkv5.dim() == 5 && qkv5.size(3) >= 3, "kv_write_multi: qkv [sq, b, g, r + 2, hd]");
+  const int64_t sq = qkv5.size(0), b = qkv5.size(1), g = qkv5.size(2), r = qkv5.size(3) - 2,
+                hd = qkv5.size(4);
+  TORCH_CHECK(sq >= 1 && sq <= 16 && (hd == 64 || hd == 128) && sq * b * g < (1ll << 31),
+              "kv_write_multi: sq in 1..16, head_dim 64 or 128");
+  TORCH_CHECK(qkv5.stride(4) == 1 && qkv5.stride(3) % 8 == 0 && qkv5.stride(2) % 8 == 0 &&
+                  qkv5.stride(1) % 8 == 0 && qkv5.stride(0) % 8 == 0,
+              "kv_write_multi: qkv strides must keep 16-byte alignment");
+  check_vec_aligned(qkv5, "qkv");
+  ema::KvWriteMultiParams p{};
+  const bool fp8 = kcache.scalar_type() == at::kByte;
+  for (const at::Tensor* c : {&kcache, &vcache}) {
+    TORCH_CHECK(c->device() == dev && c->scalar_type() == (fp8 ? at::kByte : qkv5.scalar_type()) &&
+                    c->dim() == 4 && c->size(1) >= b && c->size(2) == g && c->size(3) == hd &&
+                    c->stride(3) == 1 && c->stride(2) == hd && c->stride(1) % 16 == 0 &&
+                    c->stride(0) % 16 == 0 && reinterpret_cast<uintptr_t>(c->data_ptr()) % 16 == 0,
+                "kv_write_multi: caches [L, B, g, hd] of qkv's dtype or uint8, packed heads");
+  }
+  TORCH_CHECK(kcache.sizes() == vcache.sizes() && kcache.strides() == vcache.strides(),
+              "kv_write_multi: k / v cache shapes differ");
+  if (fp8) {
+    TORCH_CHECK(kv_scale.has_value(), "kv_write_multi: an e4m3 cache needs kv_scale");
+    p.scales = kv_scale_ptr(*kv_scale, g, qkv5);
+  }
+  if (cos.has_value() && cos->defined()) {
+    TORCH_CHECK(sin.has_value() && pos.has_value(), "kv_write_multi: cos needs sin and pos");
+    TORCH_CHECK(cos->device() == dev && sin->device() == dev && cos->scalar_type() == at::kFloat &&
+                    sin->scalar_type() == at::kFloat && cos->is_contiguous() &&
+                    sin->is_contiguous() && cos->dim() == 2 && cos->sizes() == sin->sizes() &&
+                    cos->size(0) >= 1 && cos->size(1) == hd / 2,
+                "kv_write_multi: rope tables contiguous fp32 [max_pos, hd / 2]");
+    TORCH_CHECK(pos->device() == dev && pos->scalar_type() == at::kLong && pos->dim() == 2 &&
+                    pos->size(0) == b && pos->size(1) == sq && pos->stride(1) == 1,
+                "kv_write_multi: position_ids int64 [b, sq]");
+    p.cos = cos->data_ptr<float>();
+    p.sin = sin->data_ptr<float>();
+    p.pos = pos->data_ptr<int64_t>();
+    p.pos_sb = pos->stride(0);
+    p.max_pos = cos->size(0);
+  }
+  TORCH_CHECK(slot.device() == dev && slot.scalar_type() == at::kLong && slot.is_contiguous() &&
+                  (slot.numel() == 1 || slot.numel() == b),
+              "kv_write_multi: slot int64, one element or one per sequence");
+  p.slot = slot.data_ptr<int64_t>();
+  p.slot_sb = slot.numel() == b && b > 1 ? 1 : 0;
+  if (page_table.has_value() && page_table->defined()) {
+    TORCH_CHECK(page_table->device() == dev && page_table->scalar_type() == at::kInt &&
+                    page_table->dim() == 2 && page_table->is_contiguous() &&
+                    page_table->size(0) >= b && page_table->size(1) >= 1,
+                "kv_write_multi: page_table int32 [b, pages_per_row]");
+    TORCH_CHECK(slot.numel() == b && kv_len.has_value() && kv_len->device() == dev &&
+                    kv_len->scalar_type() == at::kInt && kv_len->is_contiguous() &&
+                    (kv_len->numel() == 1 || kv_len->numel() == b),
+                "kv_write_multi: paged needs a slot per sequence and kv_len int32 (1 or b)");
+    TORCH_CHECK(b == 1 || kcache.stride(1) == 0, "kv_write_multi: paged caches are the pool (stride-0 batch)");
+    p.page_table = page_table->data_ptr<int>();
+    p.pt_ld = (int)page_table->size(1);
+    p.kv_len = kv_len->data_ptr<int>();
+    p.kv_len_sb = kv_len->numel() == b && b > 1 ? 1 : 0;
+  }
+  p.qkv = qkv5.data_ptr();
+  p.q_ss = qkv5.stride(0); p.q_sb = qkv5.stride(1); p.q_sg = qkv5.stride(2); p.q_sh = qkv5.stride(3);
+  p.kcache = kcache.data_ptr(); p.vcache = vcache.data_ptr();
+  p.c_ss = kcache.stride(0); p.c_sb = kcache.stride(1); p.L = kcache.size(0);
+  p.sq = (int)sq; p.b = (int)b; p.g = (int)g; p.r = (int)r; p.hd = (int)hd;
+  ema::kv_write_multi(p, dtype_code(qkv5), cur_stream());
+}
+
 // qkv decode projection: returns the rotated q [M, ng * r * hd]; k / v rows go
 // to kcache / vcache [L, B, ng, hd] (views at the batch offset) at the slot
 // `slot_t` (int64 device scalar, or M > 1 elements: row m's slot) or `slot`.
@@ -1462,10 +1548,14 @@ void ragged_tail(const at::Tensor& logits, at::Tensor tokens, at::Tensor history
 // hist_len / limit / accepted int64 [b], kv_len / active int32 [b], history
 // int64 [b, H], tick int64 [1], ctl int64 [3] = [stop_id, ngram, still active
 // (written)], am int32 [b, S] (scratch), counters int32 [b + 1] (zeroed once).
-void spec_tail(const at::Tensor& logits, at::Tensor tokens, at::Tensor pos, at::Tensor slot,
-               at::Tensor kv_len, at::Tensor history, at::Tensor hist_len, at::Tensor limit,
-               at::Tensor active, at::Tensor accepted, at::Tensor tick, at::Tensor ctl,
-               at::Tensor am, at::Tensor counters) {
+// fctl / gen0 (spec_sample_tail): the sampling form, ctl int64 [7] = [stop_id,
+// ngram, still active, seed, offset0, top_k, vocab_limit], fctl float32 [2] =
+// [temperature, top_p], gen0 int64 [b] the history index of noise index 0.
+static void spec_tail_impl(const at::Tensor& logits, at::Tensor tokens, at::Tensor pos,
+                           at::Tensor slot, at::Tensor kv_len, at::Tensor history,
+                           at::Tensor hist_len, at::Tensor limit, at::Tensor active,
+                           at::Tensor accepted, at::Tensor tick, at::Tensor ctl, at::Tensor am,
+                           at::Tensor counters, const at::Tensor* fctl, const at::Tensor* gen0) {
   const int dt = check_sample_logits(logits, "spec_tail");
   const auto dev = logits.device();
   TORCH_CHECK(tokens.dim() == 2, "spec_tail: tokens [b, S]");
@@ -1487,7 +1577,12 @@ void spec_tail(const at::Tensor& logits, at::Tensor tokens, at::Tensor pos, at::
                   history.size(1) < (1ll << 31), "spec_tail: history int64 [b, H]");
   TORCH_CHECK(tick.device() == dev && tick.scalar_type() == at::kLong && tick.numel() == 1 &&
                   ctl.device() == dev && ctl.scalar_type() == at::kLong && ctl.is_contiguous() &&
-                  ctl.numel() == 3, "spec_tail: tick int64 [1], ctl int64 [3]");
+                  ctl.numel() == (fctl ? 7 : 3), "spec_tail: tick int64 [1], ctl int64 [3] ([7] to sample)");
+  if (fctl)
+    TORCH_CHECK(fctl->device() == dev && fctl->scalar_type() == at::kFloat && fctl->is_contiguous() &&
+                    fctl->numel() == 2 && gen0->device() == dev && gen0->scalar_type() == at::kLong &&
+                    gen0->is_contiguous() && gen0->numel() == b,
+                "spec_sample_tail: fctl float32 [2], gen0 int64 [b]");
   TORCH_CHECK(am.device() == dev && am.scalar_type() == at::kInt && am.is_contiguous() &&
                   am.numel() == b * S && counters.device() == dev &&
                   counters.scalar_type() == at::kInt && counters.is_contiguous() &&
@@ -1497,8 +1592,26 @@ void spec_tail(const at::Tensor& logits, at::Tensor tokens, at::Tensor pos, at::
                    history.stride(0), (int)history.size(1), hist_len.data_ptr<int64_t>(),
                    limit.data_ptr<int64_t>(), active.data_ptr<int>(), accepted.data_ptr<int64_t>(),
                    tick.data_ptr<int64_t>(), ctl.data_ptr<int64_t>(), am.data_ptr<int>(),
-                   reinterpret_cast<unsigned*>(counters.data_ptr<int>())};
+                   reinterpret_cast<unsigned*>(counters.data_ptr<int>()),
+                   fctl ? fctl->data_ptr<float>() : nullptr,
+                   gen0 ? gen0->data_ptr<int64_t>() : nullptr};
   ema::spec_tail(logits.data_ptr(), logits.stride(0), (int)V, (int)S, dt, st, cur_stream());
+}
+
+void spec_tail(const at::Tensor& logits, at::Tensor tokens, at::Tensor pos, at::Tensor slot,
+               at::Tensor kv_len, at::Tensor history, at::Tensor hist_len, at::Tensor limit,
+               at::Tensor active, at::Tensor accepted, at::Tensor tick, at::Tensor ctl,
+               at::Tensor am, at::Tensor counters) {
+  spec_tail_impl(logits, tokens, pos, slot, kv_len, history, hist_len, limit, active, accepted, tick,
+                 ctl, am, counters, nullptr, nullptr);
+}
+
+void spec_sample_tail(const at::Tensor& logits, at::Tensor tokens, at::Tensor pos, at::Tensor slot,
+                      at::Tensor kv_len, at::Tensor history, at::Tensor hist_len, at::Tensor limit,
+                      at::Tensor active, at::Tensor accepted, at::Tensor tick, at::Tensor ctl,
+                      at::Tensor fctl, at::Tensor gen0, at::Tensor am, at::Tensor counters) {
+  spec_tail_impl(logits, tokens, pos, slot, kv_len, history, hist_len, limit, active, accepted, tick,
+                 ctl, am, counters, &fctl, &gen0);
 }
 
 // One draw per row of logits [b, V] into tokens int64 [b]; no tail state, the
@@ -1902,6 +2015,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("slot"), py::arg("kv_len"), py::arg("history"), py::arg("hist_len"),
         py::arg("limit"), py::arg("active"), py::arg("accepted"), py::arg("tick"), py::arg("ctl"),
         py::arg("am"), py::arg("counters"));
+  m.def("spec_sample_tail", &spec_sample_tail, py::arg("logits"), py::arg("tokens"), py::arg("pos"),
+        py::arg("slot"), py::arg("kv_len"), py::arg("history"), py::arg("hist_len"),
+        py::arg("limit"), py::arg("active"), py::arg("accepted"), py::arg("tick"), py::arg("ctl"),
+        py::arg("fctl"), py::arg("gen0"), py::arg("am"), py::arg("counters"));
+  m.def("kv_write_multi", &kv_write_multi, py::arg("qkv5"), py::arg("cos"), py::arg("sin"),
+        py::arg("pos"), py::arg("kcache"), py::arg("vcache"), py::arg("slot"),
+        py::arg("kv_len") = py::none(), py::arg("kv_scale") = py::none(),
+        py::arg("page_table") = py::none());
   m.attr("KV_PAGE") = (int)ema::KV_PAGE;
   m.def("sample_rows", &sample_rows, py::arg("logits"), py::arg("tokens"), py::arg("seed"),
         py::arg("offset"), py::arg("top_k"), py::arg("top_p"), py::arg("temperature"),

@@ -40,6 +40,42 @@ __device__ __forceinline__ void st16(T* p, const V16<T>& v) {
   *reinterpret_cast<V16<T>*>(p) = v;
 }
 
+// RoPE of one 16-byte vector of a 16-bit type: 4 interleaved pairs (x[2i],
+// x[2i+1]) by the angles whose cos / sin are c / sn, in fp32, rounded back to
+// T: the one rotation of rope.hip and kv_write_multi.hip, whose results must
+// agree to the bit.  The fused multiply-adds are spelled out, both taking the
+// product with c: left to the compiler, x0 c - x1 sn became an fma in one
+// kernel and a multiply and subtract in another.  For fp16 the fp32 result
+// also passes an empty asm, so that its rounding stays a separate convert and
+// is not folded into v_fma_mixlo_f16 in some instantiations only.
+template <typename T>
+__device__ __forceinline__ void rope_rot8(V16<T>& v, const float (&c)[4], const float (&sn)[4]) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float x0 = to_f(v.v[2 * i]), x1 = to_f(v.v[2 * i + 1]);
+    float re = __builtin_fmaf(x0, c[i], -(x1 * sn[i])), im = __builtin_fmaf(x1, c[i], x0 * sn[i]);
+    if constexpr (__is_same(T, fp16)) asm volatile("" : "+v"(re), "+v"(im));
+    v.v[2 * i] = from_f<T>(re);
+    v.v[2 * i + 1] = from_f<T>(im);
+  }
+}
+
+// 8 values -> 8 e4m3fn bytes of the FP8 KV cache: e4m3_rne(clamp(x * inv,
+// +-448)), inv = 1 / scale (the clamp first: the convert alone turns an
+// overflow into NaN); kv_store_fp8_k and kv_write_multi_k
+__device__ __forceinline__ uint2 e4m3_pack8(const float (&x)[8], float inv) {
+  float f[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) f[e] = fminf(fmaxf(x[e] * inv, -448.f), 448.f);
+  int lo = 0, hi = 0;
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
+  lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
+  hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
+  return make_uint2((unsigned)lo, (unsigned)hi);
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

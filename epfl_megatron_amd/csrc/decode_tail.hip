@@ -15,6 +15,7 @@
 // spec_tail_k (inference/speculative.py) is the tail of a speculative greedy
 // step: S logits rows per sequence, one workgroup each, and the last of a
 // sequence's workgroups to arrive verifies the drafts, commits and drafts anew.
+// spec_sample_tail_k is that tail with draw_row in place of the argmax.
 //
 // Reference: megatron/text_generation/generation.py:179-264 samples on the
 // host-driven loop (greedy = argmax of the last position's logits).
@@ -540,11 +541,27 @@ __global__ __launch_bounds__(1024) void ragged_tail_k(const T* __restrict__ logi
 // then arrives at counters[b], the finisher of a sequence that goes on with
 // 1 << 16 on top; the last one advances *tick, writes the number of sequences
 // still active to ctl[2] and re-arms (each sequence's finisher re-armed its own).
+//
+// spec_sample_tail_k (SAMPLE, SpeculativeSamplingDecoder) is the same tail for
+// sampled requests: a[t] is draw_row of row t (sample_tail_k's draw: tempered,
+// the radix-descent top-k / top-p threshold, Gumbel-max; the plain argmax at
+// top_k == 1), clamped to vocab_limit before it is compared or committed.  A
+// draft is accepted iff it IS the token drawn from the row before it: with a
+// deterministic draft that is exact speculative sampling (it is accepted with
+// probability p(draft), and otherwise the committed token is distributed as p),
+// so no softmax denominator and no second draw.  The noise of row t belongs to
+// the token it would commit, generated token n = hist_len[r] + t - gen0[r] of
+// sequence r: Philox counter row r, offset offset0 + n, the pair
+// GraphedSamplingDecoder uses for that token.  Identical logits rows hence give
+// the lockstep sampler's sequence token for token, whatever S or ngram is; the
+// row behind a rejected draft draws at the same index again in the next step.
+// Settings from the device: ctl int64 [7] = [stop_id, ngram, still active
+// (written), seed, offset0, top_k, vocab_limit], fctl = [temperature, top_p].
 constexpr int SPEC_MAX_G = 4;
 
-template <typename T>
-__global__ __launch_bounds__(1024) void spec_tail_k(const T* __restrict__ logits, int64_t ld, int V,
-                                                   int S, SpecTail st) {
+template <typename T, bool SAMPLE>
+__device__ __forceinline__ void spec_tail_body(const T* __restrict__ logits, int64_t ld, int V, int S,
+                                               const SpecTail& st) {
   const int r = blockIdx.x / S, t = blockIdx.x % S, tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   __shared__ int last_sh, hl_sh, a_sh[16], best_sh[1024 / 64][SPEC_MAX_G];
@@ -552,7 +569,17 @@ __global__ __launch_bounds__(1024) void spec_tail_k(const T* __restrict__ logits
   unsigned still = 0u;
   bool finisher = false;
   if (st.active[r] != 0) {  // (the finisher alone writes it, after all S have read it)
-    const int bi = argmax_row<T>(logits + ((int64_t)r * S + t) * ld, V, tid);
+    const T* lr = logits + ((int64_t)r * S + t) * ld;
+    int bi;
+    if constexpr (SAMPLE) {
+      // hist_len[r], as active[r]: written by the finisher alone, after every
+      // row's arrival, and the arrival follows the store of the token drawn here
+      const SampleArgs a{st.ctl[3], st.ctl[4], st.ctl[5], st.ctl[6], st.ctl[0], st.fctl[0], st.fctl[1]};
+      bi = draw_row<T>(lr, V, r, tid, a, st.hist_len[r] + t - st.gen0[r]);
+      if (a.vocab_limit > 0 && bi >= a.vocab_limit) bi = (int)a.vocab_limit - 1;
+    } else {
+      bi = argmax_row<T>(lr, V, tid);
+    }
     if (tid == 0) {
       __hip_atomic_store(st.am + r * S + t, bi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -656,12 +683,28 @@ __global__ __launch_bounds__(1024) void spec_tail_k(const T* __restrict__ logits
   }
 }
 
+template <typename T>
+__global__ __launch_bounds__(1024) void spec_tail_k(const T* __restrict__ logits, int64_t ld, int V,
+                                                   int S, SpecTail st) {
+  spec_tail_body<T, false>(logits, ld, V, S, st);
+}
+
+template <typename T>
+__global__ __launch_bounds__(1024) void spec_sample_tail_k(const T* __restrict__ logits, int64_t ld,
+                                                          int V, int S, SpecTail st) {
+  spec_tail_body<T, true>(logits, ld, V, S, st);
+}
+
 }  // namespace
 
 void spec_tail(const void* logits, int64_t ld, int V, int S, int dt, const SpecTail& st, hipStream_t s) {
   EMA_DISPATCH_FLOAT(dt, T, {
-    hipLaunchKernelGGL((spec_tail_k<T>), dim3((unsigned)(st.b * S)), dim3(1024), 0, s, (const T*)logits,
-                       ld, V, S, st);
+    if (st.fctl)
+      hipLaunchKernelGGL((spec_sample_tail_k<T>), dim3((unsigned)(st.b * S)), dim3(1024), 0, s,
+                         (const T*)logits, ld, V, S, st);
+    else
+      hipLaunchKernelGGL((spec_tail_k<T>), dim3((unsigned)(st.b * S)), dim3(1024), 0, s, (const T*)logits,
+                         ld, V, S, st);
   });
 }
 

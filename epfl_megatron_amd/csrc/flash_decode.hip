@@ -516,15 +516,10 @@ __global__ __launch_bounds__(256) void kv_store_fp8_k(const KvStoreParams p) {
   const int64_t slot = p.slot_ptr ? p.slot_ptr[bb * p.slot_sb] : p.slot;
   float f[8];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) f[e] = fminf(fmaxf((float)x[e] * inv, -448.f), 448.f);
-  int lo = 0, hi = 0;
-  lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], lo, false);
-  lo = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], lo, true);
-  hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[4], f[5], hi, false);
-  hi = __builtin_amdgcn_cvt_pk_fp8_f32(f[6], f[7], hi, true);
+  for (int e = 0; e < 8; ++e) f[e] = (float)x[e];
   uint8_t* dst = (isv ? p.vcache : p.kcache) + (slot + s) * p.c_ss + (int64_t)bb * p.c_sb +
                  (int64_t)g * p.hd + 8 * c;
-  *reinterpret_cast<uint2*>(dst) = make_uint2((unsigned)lo, (unsigned)hi);
+  *reinterpret_cast<uint2*>(dst) = e4m3_pack8(f, inv);
 }
 
 }  // namespace

@@ -284,6 +284,41 @@ struct KvStoreParams {
 };
 void kv_store_fp8(const KvStoreParams& p, int dt, hipStream_t s);
 
+// ---- kv_write_multi.hip: front of the device-slot multi-row step, one launch per layer ----------
+// qkv [sq, b, g, r + 2, hd] of dt (bf16 / fp16; element strides q_ss / q_sb /
+// q_sg / q_sh, hd 64 or 128 contiguous): the r query heads and the key head of
+// every group are rotated in place (cos / sin fp32 [max_pos, hd / 2] at pos[m *
+// pos_sb + t], clamped to the table; nullptr: no rotation), and row t of
+// sequence m of the rotated K and of V goes to cache row slot[m * slot_sb] + t
+// of kcache / vcache [L, b, g, hd] (strides c_ss / c_sb in elements of the
+// cache's type, packed heads).  page_table (int32 [b][pt_ld]): the caches are
+// the pool (c_sb == 0), row 0 goes to slot[m] and row t >= 1 to the pool row of
+// logical position kv_len[m * kv_len_sb] - sq + t, table index clamped to
+// [0, pt_ld).  scales (fp32 [2, g]; nullptr: a cache of dt): e4m3 caches,
+// byte = e4m3_rne(clamp(x / scale, +-448)) as KvStoreParams.  A row whose slot
+// is outside [0, L) is not stored.  Every slot, length and table entry is read
+// on the device.
+struct KvWriteMultiParams {
+  void* qkv;
+  int64_t q_ss, q_sb, q_sg, q_sh;
+  const float* cos;
+  const float* sin;
+  const int64_t* pos;
+  int64_t pos_sb, max_pos;
+  void* kcache;
+  void* vcache;
+  int64_t c_ss, c_sb, L;
+  const int64_t* slot;
+  int slot_sb;
+  const int* kv_len;
+  int kv_len_sb;
+  const int* page_table;
+  int pt_ld;
+  const float* scales;
+  int sq, b, g, r, hd;
+};
+void kv_write_multi(const KvWriteMultiParams& p, int dt, hipStream_t s);
+
 // ---- decode_tail.hip -----------------------------------------------------------------------------
 // Graphed greedy decode step tail: argmax of each row of logits [b, V] (row
 // stride ld) -> tokens[b], history[b, *step_idx], pos[b] += 1; the last
@@ -348,6 +383,12 @@ struct SpecTail {
   int64_t* ctl;
   int* am;
   unsigned* counters;
+  // the sampling form (spec_sample_tail_k; nullptr: the greedy one): ctl is
+  // then int64 [7] = [stop_id, ngram, still active, seed, offset0, top_k,
+  // vocab_limit], fctl float [temperature, top_p], and gen0 [b] the history
+  // index of each sequence's first generated token (its noise index 0)
+  const float* fctl;
+  const int64_t* gen0;
 };
 void spec_tail(const void* logits, int64_t ld, int V, int S, int dt, const SpecTail& st, hipStream_t s);
 int flash_decode_splits(int sk, int kpw);

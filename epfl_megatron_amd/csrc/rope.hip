@@ -47,12 +47,7 @@ __global__ __launch_bounds__(256) void rope_k(T* __restrict__ qkv, const float* 
   const float ssn[4] = {sn.x, sn.y, sn.z, sn.w};
   if constexpr (sizeof(T) == 2) {
     V16<T> v = ld16(ptr);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float x0 = to_f(v.v[2 * i]), x1 = to_f(v.v[2 * i + 1]);
-      v.v[2 * i] = from_f<T>(x0 * cc[i] - x1 * ssn[i]);
-      v.v[2 * i + 1] = from_f<T>(x0 * ssn[i] + x1 * cc[i]);
-    }
+    rope_rot8(v, cc, ssn);  // (common.h: shared with kv_write_multi.hip, bit for bit)
     st16(ptr, v);
   } else {
 #pragma unroll

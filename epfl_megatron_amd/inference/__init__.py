@@ -4,4 +4,4 @@ from .api import (beam_search, beam_search_and_post_process, generate,  # noqa: 
                   generate_and_post_process)
 from .continuous import (ContinuousBatcher, RaggedGreedyDecoder,  # noqa: F401
                          RaggedSamplingDecoder)
-from .speculative import SpeculativeGreedyDecoder  # noqa: F401
+from .speculative import SpeculativeGreedyDecoder, SpeculativeSamplingDecoder  # noqa: F401

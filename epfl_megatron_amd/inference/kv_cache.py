@@ -19,8 +19,11 @@ The cells that exist, by ``step_kind`` (``LayerKV._check`` refuses the rest):
   paged: physical, and the later rows through the table) and
   ``flash_decode_cached`` reads ``ip.device_kv_len`` keys, the count after the
   ``sq`` rows.  No host value is read.  Not with the fused decode layer, not
-  with FP8 calibration.  Caller: ``SpeculativeGreedyDecoder``
-  (``inference/speculative.py``), whose verify step is this cell.
+  with FP8 calibration.  On the GPU (bf16 / fp16, head dim 64 / 128) RoPE and
+  the write are one launch, ``write_multi_native`` (``csrc/kv_write_multi.hip``);
+  elsewhere the layer's RoPE pass and ``_write_multi`` in torch.  Callers: the
+  speculative decoders (``inference/speculative.py``), whose verify step is
+  this cell.
 - eager decode step: host slot ``s0``.  Not paged.
 - restart prefill: host slot 0; attends over the fresh K / V (16-bit columns:
   over the cached rows).  Paged: one row, scattered by its table.
@@ -38,6 +41,7 @@ import os
 import torch
 
 from ..ops import fp8_kv
+from ..ops._ext import ext, use_native
 from ..ops.attention import (flash_attn_fp8_kv, flash_attn_func, flash_attn_paged,
                              flash_decode_cached)
 from .paged import KV_PAGE, gather_rows, physical_slots
@@ -49,6 +53,10 @@ from .paged import KV_PAGE, gather_rows, physical_slots
 # scales from the prompt; else they stay 1.0.
 FP8_KV = os.environ.get("EMA_FP8_KV", "0") == "1"
 FP8_KV_CALIBRATE = os.environ.get("EMA_FP8_KV_CALIBRATE", "0") == "1"
+# The multi-row device step's RoPE + cache write in one HIP launch
+# (LayerKV.write_multi_native); off: the separate RoPE pass and _write_multi in
+# torch, bit for bit the same cache (scripts/serve_bench.py --torch_front times both)
+WRITE_MULTI_NATIVE = os.environ.get("EMA_KV_WRITE_MULTI", "1") == "1"
 
 
 def set_fp8_kv_cache(on, calibrate=None):
@@ -218,6 +226,40 @@ class LayerKV:
         else:
             kc.index_copy_(0, slots, k)
             vc.index_copy_(0, slots, v)
+
+    def write_multi_native(self, qkv5, rope, position_ids):
+        """The front of a multi-row device step in one HIP launch
+        (``csrc/kv_write_multi.hip``): RoPE of the q and k heads of the packed
+        projection ``qkv5 [sq, b, g, r + 2, hd]`` in place (``rope``: the
+        ``(cos, sin)`` tables or None) and the cache write of its k / v rows,
+        as ``write`` does it after the separate RoPE pass, bit for bit.  False
+        when the kernel does not take the call (``WRITE_MULTI_NATIVE`` off,
+        CPU, fp32, another head dim, strides that lose the 16-byte alignment,
+        RoPE without ``[b, sq]`` position ids or with tables of another width,
+        a key count that is not int32): the caller then rotates and calls
+        ``write``."""
+        sq, b, hd = qkv5.shape[0], qkv5.shape[1], qkv5.shape[-1]
+        ok = (WRITE_MULTI_NATIVE and self.kind == DEVICE_MULTI and self.native and use_native(qkv5)
+              and qkv5.dtype in (torch.bfloat16, torch.float16) and qkv5.stride(-1) == 1
+              and all(s % 8 == 0 for s in qkv5.stride()[:4]) and qkv5.data_ptr() % 16 == 0
+              and self.kmem.dtype in (qkv5.dtype, torch.uint8)
+              and not (torch.is_grad_enabled() and qkv5.requires_grad))
+        if ok and rope is not None:
+            ok = (position_ids is not None and tuple(position_ids.shape) == (b, sq)
+                  and not position_ids.dtype.is_floating_point
+                  and all(t.dtype == torch.float32 and t.is_contiguous()
+                          and tuple(t.shape[1:]) == (hd // 2,) for t in rope))
+        if ok and self.paged:
+            ok = self.ip.device_kv_len.dtype == torch.int32 and self.table.dtype == torch.int32
+        if not ok:
+            return False
+        cos, sin = rope if rope is not None else (None, None)
+        pos = None if rope is None else position_ids.long().contiguous()
+        ext().kv_write_multi(qkv5, cos, sin, pos, self.kc, self.vc,
+                             self.slot_t.reshape(-1).long().contiguous(),
+                             self.ip.device_kv_len.reshape(-1).contiguous() if self.paged else None,
+                             self.scales, self.table.contiguous() if self.paged else None)
+        return True
 
     def _write_multi(self, k, v):
         """The ``sq`` rows of a multi-row device step: row ``t`` of sequence ``m``

@@ -1,11 +1,12 @@
-"""Speculative greedy decode on one captured hipGraph: n-gram (prompt-lookup)
-drafts, verified by the multi-row device step.
+"""Speculative decode on one captured hipGraph, greedy or sampled: n-gram
+(prompt-lookup) drafts, verified by the multi-row device step.
 
 A decode step at small batch is a weight stream that costs the same for one
 row per sequence or for eight.  ``SpeculativeGreedyDecoder`` feeds ``S`` rows per
 sequence: the last committed token and ``D = S - 1`` drafted continuations.  The
 forward is the "device-slot multi-row step" cell of ``inference/kv_cache.py``
-(the unfused layer, ``_write_multi``, ``flash_decode_cached`` with ``sq = S``:
+(the unfused layer, RoPE and the cache write in one launch,
+``csrc/kv_write_multi.hip``, then ``flash_decode_cached`` with ``sq = S``:
 ``csrc/flash_decode_mq.hip``), and the tail (``spec_tail_k``,
 ``csrc/decode_tail.hip``) takes the argmax of all ``S`` logits rows, accepts the
 drafts that the model itself would have produced, commits them and the one
@@ -22,26 +23,32 @@ step depends on is a device tensor (``spec_tail_k``'s comment lists them).
 
 Not built: the fused decode layer at more than one row per sequence (a step
 here runs the unfused layer, so a step costs more than a lockstep greedy
-step; speculation pays only when drafts are accepted), sampling (rejection
-sampling), a draft model, tree drafts, the continuous batcher and paged caches,
-the text-generation API / server flag, a HIP form of ``_write_multi``.
+step; speculation pays only when drafts are accepted), a draft model, tree
+drafts, the continuous batcher and paged caches, the text-generation API /
+server flag, sampling settings per row.
+
+``SpeculativeSamplingDecoder`` is the same loop for sampled requests: its tail
+(``spec_sample_tail_k``) draws every row with ``sample_tail_k``'s draw and
+accepts a draft iff it is the token drawn before it (class docstring).
 """
 import torch
 
+from ..ops.sampling import _next_seed_offset, sample_ref
 from ..parallel import state
 from . import kv_cache
-from .hip_graph import _check_unpaged
+from .hip_graph import _check_unpaged, broadcast_seed_offset
 
 MAX_NGRAM = 4
 
 
 def spec_tail_ref(logits, tokens, pos, slot, kv_len, history, hist_len, limit, active, accepted,
-                  tick, ctl):
+                  tick, ctl, am=None):
     """``spec_tail_k`` in plain torch, in place on the state tensors: ``logits
     [b * S, V]``, ``tokens / pos [b, S]``, the others per sequence; ``ctl =
-    [stop_id, ngram, sequences still active (written)]``."""
+    [stop_id, ngram, sequences still active (written)]``.  ``am [b, S]``: the
+    token of every row where it is not the argmax (``spec_sample_tail_ref``)."""
     b, S = tokens.shape
-    am = logits.argmax(-1).view(b, S).tolist()
+    am = (logits.argmax(-1).view(b, S) if am is None else am).tolist()
     stop_id, G = int(ctl[0]), min(max(int(ctl[1]), 0), MAX_NGRAM)
     still = 0
     for r in range(b):
@@ -77,6 +84,27 @@ def spec_tail_ref(logits, tokens, pos, slot, kv_len, history, hist_len, limit, a
         kv_len[r] = nl - 1 + S
     tick += 1
     ctl[2] = still
+
+
+def spec_sample_tail_ref(logits, tokens, pos, slot, kv_len, history, hist_len, limit, active,
+                         accepted, tick, ctl, fctl, gen0):
+    """``spec_sample_tail_k`` in fp64 / torch (CPU), in place as ``spec_tail_ref``:
+    row ``t`` of sequence ``r`` draws with ``sample_ref`` at the noise index of
+    the token it would commit, Philox row ``r`` and step ``hist_len[r] + t -
+    gen0[r]``, and the greedy tail's bookkeeping runs on the drawn tokens.
+    ``ctl = [stop_id, ngram, still active (written), seed, offset0, top_k,
+    vocab_limit]``, ``fctl = [temperature, top_p]``."""
+    b, S = tokens.shape
+    seed, offset0, top_k, vocab = (int(x) for x in ctl[3:7])
+    x, drawn = logits.detach().float().cpu(), torch.zeros(b, S, dtype=torch.long)
+    for r in range(b):
+        for t in range(S if int(active[r]) else 0):
+            # sample_ref numbers its rows from 0: row r of r + 1 copies is Philox row r
+            drawn[r, t] = sample_ref(x[r * S + t].expand(r + 1, -1), seed, offset0,
+                                     int(hist_len[r]) + t - int(gen0[r]), top_k, float(fctl[1]),
+                                     float(fctl[0]), vocab or None)[r]
+    spec_tail_ref(logits, tokens, pos, slot, kv_len, history, hist_len, limit, active, accepted,
+                  tick, ctl, am=drawn)
 
 
 class SpeculativeGreedyDecoder:
@@ -151,14 +179,20 @@ class SpeculativeGreedyDecoder:
         logits = self._forward()
         flat = logits.reshape(self.batch * self.rows, -1)
         if self._fused_tail(flat):
-            from ..ops._ext import ext
-            ext().spec_tail(flat, *self._state(), self.am, self.counters)
+            self._tail(flat, True)
         elif self.graph_mode:
             raise RuntimeError("the speculative tail needs bf16 / fp16 / fp32 logits on the GPU "
                                "with 16-byte aligned rows")
         else:
-            spec_tail_ref(flat, *self._state())
+            self._tail(flat, False)
         return logits
+
+    def _tail(self, flat, native):
+        if native:
+            from ..ops._ext import ext
+            ext().spec_tail(flat, *self._state(), self.am, self.counters)
+        else:
+            spec_tail_ref(flat, *self._state())
 
     def start(self, prompt_tokens, next_tokens, stop_id=-1):
         """Seed the context with the prefilled ``prompt_tokens [batch, L]`` and
@@ -188,7 +222,7 @@ class SpeculativeGreedyDecoder:
             self.accepted.zero_()
             self.tick.zero_()
             self.active.fill_(1)
-            self.ctl.copy_(torch.tensor([stop_id, self.ngram, b]))
+            self.ctl[:3].copy_(torch.tensor([stop_id, self.ngram, b]))
             ip.device_offset, ip.device_kv_len, ip.device_multi = self.slot, self.kv_len, True
             if self.graph_mode and self.graph is None:
                 self._capture()
@@ -230,3 +264,75 @@ class SpeculativeGreedyDecoder:
     def mean_accepted(self):
         """Accepted drafts per sequence and step so far (reads the device)."""
         return float(self.accepted.sum()) / max(int(self.tick) * self.batch, 1)
+
+
+class SpeculativeSamplingDecoder(SpeculativeGreedyDecoder):
+    """``SpeculativeGreedyDecoder`` for sampled requests: temperature and top-k or
+    top-p, the draw inside the captured graph (``spec_sample_tail_k``).
+
+    Usage::
+
+        dec = SpeculativeSamplingDecoder(model, ip, batch, max_new_tokens, rows=8, ngram=3,
+                                         vocab_size=None)
+        dec.start(prompt_tokens, next_tokens, top_k=0, top_p=0.9, temperature=0.8, stop_id=-1)
+        while dec.active_rows():
+            dec.step()
+        tokens, lengths = dec.generated()
+
+    Every row of a step draws the token that follows it, with the noise of that
+    token's place in its sequence: Philox row = the sequence, offset =
+    ``offset0 + n`` for generated token ``n``, the pair ``GraphedSamplingDecoder``
+    uses.  A draft is accepted iff it is the token drawn before it, which for a
+    deterministic draft is exact speculative sampling, so the committed tokens
+    are distributed as the one-token-at-a-time sampler's, and for the same logits
+    they ARE its tokens.  The settings live in device tensors (``ctl``,
+    ``fctl``): a later ``start()`` with others replays the same graph.
+    ``start()`` takes ``(seed, offset0)`` from the CUDA generator (TP rank 0's)
+    and advances it past the generation, or from ``seed_offset``.  ``graph=False``
+    runs eagerly (on the CPU with ``spec_sample_tail_ref``)."""
+
+    def __init__(self, model, inference_params, batch, max_new_tokens, rows=4, ngram=3, graph=True,
+                 vocab_size=None):
+        super().__init__(model, inference_params, batch, max_new_tokens, rows, ngram, graph)
+        self.vocab_size = vocab_size
+        self.seed = self.offset0 = None
+
+    def _allocate(self, L):
+        super()._allocate(L)
+        self.ctl = torch.zeros(7, dtype=torch.long, device=self.dev)
+        self.fctl = torch.ones(2, dtype=torch.float32, device=self.dev)
+        self.gen0 = torch.full((self.batch,), L + 1, dtype=torch.long, device=self.dev)
+
+    def _tail(self, flat, native):
+        if native:
+            from ..ops._ext import ext
+            ext().spec_sample_tail(flat, *self._state(), self.fctl, self.gen0, self.am,
+                                   self.counters)
+        else:
+            spec_sample_tail_ref(flat, *self._state(), self.fctl, self.gen0)
+
+    def start(self, prompt_tokens, next_tokens, top_k=0, top_p=0.0, temperature=1.0, stop_id=-1,
+              seed_offset=None):
+        """As ``SpeculativeGreedyDecoder.start`` plus the sampling settings of
+        this generation (one setting per batch, as the text-generation API has)."""
+        if top_k < 0 or (top_k > 0 and top_p != 0.0):
+            raise AssertionError("cannot set both top-k and top-p samplings")
+        if not 0.0 <= top_p <= 1.0:
+            raise AssertionError("top-p should be in (0, 1]")
+        if not temperature > 0.0:
+            raise AssertionError("temperature should be positive")
+        if seed_offset is not None:
+            seed, offset0 = seed_offset
+        elif self.dev.type == "cuda":
+            gen = torch.cuda.default_generators[self.dev.index]
+            seed, offset0 = gen.initial_seed(), gen.get_offset()
+            # one Philox offset per generated token; the generator moves in multiples of 4
+            gen.set_offset(offset0 + (self.max_new + 4) // 4 * 4)
+        else:
+            seed, offset0 = _next_seed_offset(self.dev)
+        if self.dev.type == "cuda":
+            seed, offset0 = broadcast_seed_offset(seed, offset0, self.dev)
+        self.seed, self.offset0 = seed, offset0
+        super().start(prompt_tokens, next_tokens, stop_id=stop_id)
+        self.ctl[3:].copy_(torch.tensor([seed, offset0, top_k, self.vocab_size or 0]))
+        self.fctl.copy_(torch.tensor([temperature, top_p], dtype=torch.float32))

@@ -400,11 +400,20 @@ class ParallelAttention(MegatronModule):
 
     def _inference_forward(self, mixed, attention_mask, ip, position_ids, rope):
         s0 = ip.sequence_len_offset
+        sq_, b_ = mixed.shape[:2]
+        kv = LayerKV(ip, self.layer_number, self.num_groups_per_partition,
+                     self.hidden_size_per_attention_head, self.params_dtype, mixed.device, sq_, b_)
+        # the multi-row device step: RoPE and the cache write of its rows in one
+        # launch where the kernel takes them (LayerKV decides), else the passes below
+        if mixed.is_contiguous() and kv.write_multi_native(
+                mixed.view(sq_, b_, self.num_groups_per_partition, self.q_per_group + 2,
+                           self.hidden_size_per_attention_head), rope, position_ids):
+            q, k, v = self._split_qkv(mixed)
+            return kv.attend(q, k, v, self._window, self.use_flash_attn, None)
         if rope is not None and use_native(mixed) and mixed.is_contiguous() and \
                 not (torch.is_grad_enabled() and mixed.requires_grad):
             # one in-place HIP pass over q and k of the fused projection, with
             # the true positions, BEFORE caching (fixes D1)
-            sq_, b_ = mixed.shape[:2]
             rope_qkv_inplace(mixed.view(sq_, b_, self.num_groups_per_partition,
                                         self.q_per_group + 2, self.hidden_size_per_attention_head),
                              rope[0], rope[1], position_ids, offset=s0)
@@ -414,9 +423,6 @@ class ParallelAttention(MegatronModule):
             # Rotate with the true positions BEFORE caching (fixes D1).
             q = apply_rope_ref(q, rope[0], rope[1], position_ids, offset=s0)
             k = apply_rope_ref(k, rope[0], rope[1], position_ids, offset=s0)
-        kv = LayerKV(ip, self.layer_number, self.num_groups_per_partition,
-                     self.hidden_size_per_attention_head, self.params_dtype, mixed.device,
-                     *q.shape[:2])
         kv.write(k, v)
         return kv.attend(q, k, v, self._window, self.use_flash_attn,
                          lambda q, keys, vals: self.core_attention(

@@ -45,6 +45,8 @@ speculative.py: S rows per sequence, n-gram drafts verified in the captured
 graph) against GraphedGreedyDecoder from the same prefilled prompt, --reps
 repetitions each, alternating, once on a prompt of period 8 and once on a random
 one; reports tokens/s, ms per replay and the mean accepted drafts per step.
+With --top_k / --top_p / --temperature: SpeculativeSamplingDecoder against
+GraphedSamplingDecoder, both started from the same generator state.
 
 Usage: python scripts/serve_bench.py [--batches 1,8,32] [--graph [--speculative S [--ngram G]]]
        [--top_k K | --top_p P] [--temperature T]
@@ -117,8 +119,12 @@ def main():
     ap.add_argument("--prefill_chunk", type=int, default=0,
                     help="--prefix_share: ContinuousBatcher prefill_chunk (0: whole prompts)")
     ap.add_argument("--speculative", type=int, default=0,
-                    help="--graph: rows per sequence of SpeculativeGreedyDecoder (2..16; 0: off)")
+                    help="--graph: rows per sequence of SpeculativeGreedyDecoder, or with --top_k / "
+                         "--top_p / --temperature SpeculativeSamplingDecoder (2..16; 0: off)")
     ap.add_argument("--ngram", type=int, default=3, help="--speculative: longest n-gram looked up")
+    ap.add_argument("--torch_front", action="store_true",
+                    help="--speculative: also time the decoder captured with the multi-row step's RoPE "
+                         "and cache write in torch (kv_cache.WRITE_MULTI_NATIVE off), alternating")
     a = ap.parse_args()
     sampling = a.top_k > 0 or a.top_p > 0.0 or a.temperature != 1.0
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=os.environ.get("MASTER_PORT", "29561"),
@@ -168,7 +174,7 @@ def main():
     if a.ragged_cost:
         return ragged_cost(a, m)
     if a.graph and a.speculative:
-        return speculative(a, m)
+        return speculative(a, m, sampling, skw)
     res = []
     for B in [int(x) for x in a.batches.split(",")]:
         total = a.prompt + a.gen
@@ -441,13 +447,19 @@ def prefix_share(a, m):
     return res
 
 
-def speculative(a, m):
+def speculative(a, m, sampling, skw):
     """--graph --speculative S: tokens/s of the speculative and the lockstep
-    greedy decoder for --gen tokens after the same prompt, alternating."""
+    greedy decoder for --gen tokens after the same prompt, alternating; with
+    --top_k / --top_p / --temperature the two sampling decoders, both started
+    from the same generator state (the same noise per generated token)."""
     import torch
-    from epfl_megatron_amd.inference import SpeculativeGreedyDecoder
+    from epfl_megatron_amd.inference import SpeculativeGreedyDecoder, SpeculativeSamplingDecoder, kv_cache
     from epfl_megatron_amd.inference.forward_step import InferenceParams
-    from epfl_megatron_amd.inference.hip_graph import GraphedGreedyDecoder
+    from epfl_megatron_amd.inference.hip_graph import GraphedGreedyDecoder, GraphedSamplingDecoder
+    lock, spec_cls = (GraphedSamplingDecoder, SpeculativeSamplingDecoder) if sampling else \
+        (GraphedGreedyDecoder, SpeculativeGreedyDecoder)
+    kw = dict(vocab_size=32000) if sampling else {}
+    skw = skw if sampling else {}
     S, res = a.speculative, []
     total = a.prompt + a.gen + S
     for B in [int(x) for x in a.batches.split(",")]:
@@ -458,19 +470,23 @@ def speculative(a, m):
         for kind, prompt in prompts.items():
             prompt = prompt[:, :a.prompt].cuda()
             decs, secs, replays = {}, {"greedy": [], "speculative": []}, 0
+            if a.torch_front:  # the same decoder captured with RoPE + _write_multi in torch
+                secs["speculative_torch_front"] = []
             with torch.no_grad():
                 for name in secs:
                     ip = InferenceParams(B, total)
                     nxt = m(prompt, pos, None, inference_params=ip)[:, -1].argmax(-1)
                     ip.sequence_len_offset = a.prompt
-                    decs[name] = GraphedGreedyDecoder(m, ip, B, a.gen) if name == "greedy" else \
-                        SpeculativeGreedyDecoder(m, ip, B, a.gen, rows=S, ngram=a.ngram)
+                    decs[name] = lock(m, ip, B, a.gen, **kw) if name == "greedy" else \
+                        spec_cls(m, ip, B, a.gen, rows=S, ngram=a.ngram, **kw)
                 for rep in range(a.reps + 1):  # rep 0: capture and warm-up
                     for name, dec in decs.items():
+                        torch.cuda.manual_seed(a.seed)
+                        kv_cache.WRITE_MULTI_NATIVE = name != "speculative_torch_front"  # (read at capture)
                         if name == "greedy":
-                            dec.start(nxt.view(B, 1), a.prompt)
+                            dec.start(nxt.view(B, 1), a.prompt, **skw)
                         else:
-                            dec.start(prompt, nxt)
+                            dec.start(prompt, nxt, **skw)
 
                         def run():
                             if name == "greedy":
@@ -485,9 +501,11 @@ def speculative(a, m):
                         if rep:
                             secs[name].append(round(dt, 4))
                             replays = n if name == "speculative" else replays
+            kv_cache.WRITE_MULTI_NATIVE = True
             spec = decs["speculative"]
             toks, lens = spec.generated()
-            r = {"mode": "speculative", "batch": B, "rows": S, "ngram": a.ngram, "prompt_kind": kind,
+            r = {"mode": "speculative", "sampling": dict(skw) if sampling else None, "batch": B,
+                 "rows": S, "ngram": a.ngram, "prompt_kind": kind,
                  "prompt": a.prompt, "gen": a.gen, "mean_accepted": round(spec.mean_accepted(), 3),
                  "speculative_replays": replays,
                  "same_tokens": bool(lens.eq(a.gen).all()) and

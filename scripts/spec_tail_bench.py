@@ -1,5 +1,6 @@
-"""The speculative decode tail alone (spec_tail_k, csrc/decode_tail.hip) against the
-lockstep greedy tail (greedy_tail_k) at V = 32000, bf16, batch 1 and 8, S 4 and 8.
+"""The speculative decode tails alone (spec_tail_k and, for sampled requests at top-p 0.9 and
+temperature 0.8, spec_sample_tail_k; csrc/decode_tail.hip) against the lockstep tails
+(greedy_tail_k, sample_tail_k) at V = 32000, bf16, batch 1 and 8, S 4 and 8.
 
 ``--reps`` back-to-back launches are captured in one hipGraph and a replay is timed
 with device events, five replays per round, two rounds, the kernels alternating.
@@ -34,7 +35,17 @@ def greedy(b, reps, logits):
     return reset, lambda k: ext().greedy_tail(logits[k:k + b], *state)
 
 
-def spec(b, S, reps, logits):
+def sample(b, reps, logits):
+    state = [z(b), z(b, reps + 8), z(1), z(b), z(1), z(1, dtype=torch.int32), z(1, dtype=torch.int32),
+             torch.tensor([1234, 0, 0, 0, -1, 0], device="cuda"), torch.tensor([0.8, 0.9], device="cuda")]
+
+    def reset():
+        state[2].zero_()
+
+    return reset, lambda k: ext().sample_tail(logits[k:k + b], *state)
+
+
+def spec(b, S, reps, logits, sampled=False):
     cap = CTX + reps * S + 8
     history = torch.randint(0, V, (b, cap), device="cuda")
     tokens = history[:, CTX - 1:CTX].repeat(1, S)
@@ -48,6 +59,11 @@ def spec(b, S, reps, logits):
         for t, t0 in zip(state, init):
             t.copy_(t0)
 
+    if sampled:  # ctl grows to [stop_id, ngram, active, seed, offset0, top_k, vocab_limit]
+        init[10] = torch.tensor([-1, 3, b, 1234, 0, 0, 0], device="cuda")
+        state[10] = init[10].clone()
+        extra = [torch.tensor([0.8, 0.9], device="cuda"), z(b) + CTX]  # fctl, gen0
+        return reset, lambda k: ext().spec_sample_tail(logits[k:k + b * S], *state, *extra, *scratch)
     return reset, lambda k: ext().spec_tail(logits[k:k + b * S], *state, *scratch)
 
 
@@ -87,6 +103,8 @@ if __name__ == "__main__":
     for b in (1, 8):
         runs = {f"greedy b{b}": greedy(b, a.reps, logits)}
         runs.update({f"spec b{b} S{S}": spec(b, S, a.reps, logits) for S in (4, 8)})
+        runs[f"sample b{b}"] = sample(b, a.reps, logits)
+        runs.update({f"spec_sample b{b} S{S}": spec(b, S, a.reps, logits, True) for S in (4, 8)})
         us = {name: [] for name in runs}
         for _ in range(2):
             for name, (reset, launch) in runs.items():
