@@ -1049,7 +1049,9 @@ static at::Tensor qkv_rope_cache(const at::Tensor& x, const at::Tensor& w,
                                  at::Tensor vcache, const c10::optional<at::Tensor>& slot_t,
                                  int64_t slot, bool packed,
                                  const c10::optional<at::Tensor>& w_scale,
-                                 const c10::optional<at::Tensor>& kv_scale, int wide_fb) {
+                                 const c10::optional<at::Tensor>& kv_scale, int wide_fb,
+                                 int64_t seqs, const c10::optional<at::Tensor>& kv_len,
+                                 const c10::optional<at::Tensor>& page_table) {
   auto p = skinny_args(x, w, norm_w, eps, packed, w_scale);
   const int64_t N = w.size(0);
   TORCH_CHECK(N == ng * (r + 2) * hd && hd % 8 == 0, "skinny qkv: w rows != ng * (r + 2) * hd");
@@ -1063,16 +1065,61 @@ static at::Tensor qkv_rope_cache(const at::Tensor& x, const at::Tensor& w,
   TORCH_CHECK(cos.is_cuda() && sin.is_cuda() && cos.scalar_type() == at::kFloat &&
               sin.scalar_type() == at::kFloat && cos.is_contiguous() && sin.is_contiguous() &&
               cos.size(-1) == hd / 2, "skinny qkv: rope tables fp32 [max_pos, hd/2]");
-  TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kLong && pos.size(0) == p.M,
-              "skinny qkv: pos int64 with one row per token");
+  // multi-row geometry (SkinnyArgs::seqs): the rows are sq tokens of b = seqs
+  // sequences in [sq, b] order, validated as kv_write_multi's operands are
+  const int64_t b = seqs, sq = seqs > 0 ? p.M / seqs : 1;
+  TORCH_CHECK(seqs >= 0 && (seqs > 0 || (!kv_len && !page_table)),
+              "skinny qkv: kv_len / page_table belong to the multi-row geometry (seqs > 0)");
+  if (seqs > 0) {
+    TORCH_CHECK(sq * b == p.M && sq >= 2 && sq <= 16,
+                "skinny qkv: seqs must divide the rows into 2..16 rows per sequence");
+    TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kLong && pos.dim() == 2 &&
+                    pos.size(0) == b && pos.size(1) == sq && pos.stride(1) == 1,
+                "skinny qkv: multi-row position ids int64 [b, sq]");
+    TORCH_CHECK(cos.dim() == 2 && cos.sizes() == sin.sizes() && cos.size(0) >= 1,
+                "skinny qkv: rope tables [max_pos, hd/2]");
+  } else {
+    TORCH_CHECK(pos.is_cuda() && pos.scalar_type() == at::kLong && pos.size(0) == p.M,
+                "skinny qkv: pos int64 with one row per token");
+  }
   for (const at::Tensor* c : {&kcache, &vcache}) {
     TORCH_CHECK(c->is_cuda() && c->scalar_type() == cache_t && c->dim() == 4 &&
-                c->size(1) >= p.M && c->size(2) == ng && c->size(3) == hd && c->stride(3) == 1 &&
+                (c->size(1) >= (seqs > 0 ? b : p.M) || (seqs > 0 && c->stride(1) == 0)) &&
+                c->size(2) == ng && c->size(3) == hd && c->stride(3) == 1 &&
                 c->stride(2) == hd, "skinny qkv: caches [L, B, ng, hd] with packed heads");
   }
   TORCH_CHECK(kcache.stride(0) == vcache.stride(0) && kcache.stride(1) == vcache.stride(1),
               "skinny qkv: k / v cache strides differ");
-  if (slot_t) {
+  if (seqs > 0) {
+    const auto dev = x.device();
+    TORCH_CHECK(kcache.sizes() == vcache.sizes() && kcache.device() == dev && vcache.device() == dev &&
+                    pos.device() == dev, "skinny qkv: multi-row caches of one shape on x's device");
+    TORCH_CHECK(slot_t && slot_t->device() == dev && slot_t->scalar_type() == at::kLong &&
+                    slot_t->is_contiguous() && (slot_t->numel() == 1 || slot_t->numel() == b),
+                "skinny qkv: multi-row slot int64 on the device, one element or one per sequence");
+    p.slot_ptr = slot_t->data_ptr<int64_t>();
+    p.slot_sb = slot_t->numel() == b && b > 1 ? 1 : 0;
+    if (page_table) {
+      TORCH_CHECK(page_table->device() == dev && page_table->scalar_type() == at::kInt &&
+                      page_table->dim() == 2 && page_table->is_contiguous() &&
+                      page_table->size(0) >= b && page_table->size(1) >= 1,
+                  "skinny qkv: page_table int32 [b, pages_per_row]");
+      TORCH_CHECK(slot_t->numel() == b && kv_len && kv_len->device() == dev &&
+                      kv_len->scalar_type() == at::kInt && kv_len->is_contiguous() &&
+                      (kv_len->numel() == 1 || kv_len->numel() == b),
+                  "skinny qkv: paged needs a slot per sequence and kv_len int32 (1 or b)");
+      TORCH_CHECK(b == 1 || kcache.stride(1) == 0,
+                  "skinny qkv: paged caches are the pool (stride-0 batch)");
+      p.page_table = page_table->data_ptr<int>();
+      p.pt_ld = (int)page_table->size(1);
+      p.kv_len = kv_len->data_ptr<int>();
+      p.kv_len_sb = kv_len->numel() == b && b > 1 ? 1 : 0;
+    }
+    p.seqs = (int)b;
+    p.seqs_mul = 65536 / (int)b + 1;
+    p.L = kcache.size(0);
+    p.max_pos = (int)std::min<int64_t>(cos.size(0), INT32_MAX);
+  } else if (slot_t) {
     TORCH_CHECK(slot_t->is_cuda() && slot_t->scalar_type() == at::kLong && slot_t->numel() >= 1,
                 "skinny qkv: slot int64");
     p.slot_ptr = slot_t->data_ptr<int64_t>();
@@ -1108,9 +1155,11 @@ at::Tensor skinny_qkv_rope_cache(const at::Tensor& x, const at::Tensor& w,
                                  at::Tensor vcache, const c10::optional<at::Tensor>& slot_t,
                                  int64_t slot, bool packed,
                                  const c10::optional<at::Tensor>& w_scale,
-                                 const c10::optional<at::Tensor>& kv_scale) {
+                                 const c10::optional<at::Tensor>& kv_scale, int64_t seqs,
+                                 const c10::optional<at::Tensor>& kv_len,
+                                 const c10::optional<at::Tensor>& page_table) {
   return qkv_rope_cache(x, w, norm_w, eps, ng, r, hd, cos, sin, pos, kcache, vcache, slot_t, slot,
-                        packed, w_scale, kv_scale, -1);
+                        packed, w_scale, kv_scale, -1, seqs, kv_len, page_table);
 }
 
 // ---------------------------------------------------------------- wide GEMM (decode, 33-64 rows)
@@ -1182,9 +1231,11 @@ at::Tensor wide_qkv_rope_cache(const at::Tensor& x, const at::Tensor& w, int64_t
                                const at::Tensor& pos, at::Tensor kcache, at::Tensor vcache,
                                const c10::optional<at::Tensor>& slot_t, int64_t slot,
                                const c10::optional<at::Tensor>& w_scale,
-                               const c10::optional<at::Tensor>& kv_scale, int64_t fb) {
+                               const c10::optional<at::Tensor>& kv_scale, int64_t fb, int64_t seqs,
+                               const c10::optional<at::Tensor>& kv_len,
+                               const c10::optional<at::Tensor>& page_table) {
   return qkv_rope_cache(x, w, c10::nullopt, 0.0, ng, r, hd, cos, sin, pos, kcache, vcache, slot_t,
-                        slot, true, w_scale, kv_scale, wide_fb(fb));
+                        slot, true, w_scale, kv_scale, wide_fb(fb), seqs, kv_len, page_table);
 }
 
 // ---------------------------------------------------------------- decode attention
@@ -2070,7 +2121,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("norm_w"), py::arg("eps"), py::arg("ng"), py::arg("r"), py::arg("hd"),
         py::arg("cos"), py::arg("sin"), py::arg("pos"), py::arg("kcache"), py::arg("vcache"),
         py::arg("slot_t"), py::arg("slot"), py::arg("packed") = false,
-        py::arg("w_scale") = py::none(), py::arg("kv_scale") = py::none());
+        py::arg("w_scale") = py::none(), py::arg("kv_scale") = py::none(), py::arg("seqs") = 0,
+        py::arg("kv_len") = py::none(), py::arg("page_table") = py::none());
   m.def("wide_gemm_supported", &wide_gemm_supported);
   m.def("wide_gemm_split", &ema::wide_gemm_split, py::arg("nblocks"));
   m.def("wide_gemm", &wide_gemm, py::arg("x"), py::arg("w_packed"), py::arg("res") = py::none(),
@@ -2080,7 +2132,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("wide_qkv_rope_cache", &wide_qkv_rope_cache, py::arg("x"), py::arg("w_packed"),
         py::arg("ng"), py::arg("r"), py::arg("hd"), py::arg("cos"), py::arg("sin"), py::arg("pos"),
         py::arg("kcache"), py::arg("vcache"), py::arg("slot_t"), py::arg("slot"),
-        py::arg("w_scale") = py::none(), py::arg("kv_scale") = py::none(), py::arg("fb") = 0);
+        py::arg("w_scale") = py::none(), py::arg("kv_scale") = py::none(), py::arg("fb") = 0,
+        py::arg("seqs") = 0, py::arg("kv_len") = py::none(), py::arg("page_table") = py::none());
   m.def("transpose16", &transpose16);
   m.def("transpose16_supported", &transpose16_supported);
 }

@@ -551,6 +551,22 @@ struct SkinnyArgs {
   // in bytes) and kv_scale is fp32 [2, ng] (row 0: K, row 1: V); a k / v value
   // is stored as e4m3_rne(clamp(x / scale, +-448)).  nullptr: 16-bit caches.
   const float* kv_scale;
+  // EPI_QKV, multi-row geometry (seqs = b > 0; 0: one row per sequence, above):
+  // the M = sq * b rows are sq in 2..16 tokens of b sequences in [sq, b] order,
+  // row i = t * b + m.  Its position is pos[m * pos_sb + t] (clamped to the
+  // max_pos rows of the rotary tables), q goes to y row i, and k / v go to
+  // cache column m (m * c_sb) at slot slot_ptr[m * slot_sb] + t -- with a
+  // page_table (int32 [b][pt_ld], the caches are the pool, c_sb == 0) row t >=
+  // 1 goes to the pool row of logical position kv_len[m * kv_len_sb] - sq + t,
+  // table index clamped to [0, pt_ld).  A row whose slot is outside [0, L) is
+  // not stored: the rules of KvWriteMultiParams.  seqs_mul = 65536 / seqs + 1
+  // (i / seqs == (i * seqs_mul) >> 16 for the i < 64 rows of these kernels).
+  int seqs, seqs_mul;
+  int kv_len_sb, pt_ld;
+  const int* kv_len;
+  const int* page_table;
+  int64_t L;
+  int max_pos;
 };
 void skinny_gemm_ex(const SkinnyArgs& p, int epi, int dt, hipStream_t s);
 int skinny_glu_half_tail(int64_t F, int64_t K, bool norm, int64_t M);

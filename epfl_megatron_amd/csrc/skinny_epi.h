@@ -133,12 +133,80 @@ __device__ __forceinline__ f4 epi_scale(const SkinnyArgs& p, int blk, int half, 
   return *reinterpret_cast<const f4*>(p.w_scale + row);
 }
 
+// EPI_QKV: which geometry of SkinnyArgs the call has.  GEOM -1: read at run
+// time (p.seqs, a wave-uniform branch); 0 / 1: the kernel was compiled for one
+// row per sequence / for the multi-row geometry.  The persistent forms take
+// it as a template argument: beside their k-loop's registers the run-time
+// branch cost them 1-4 VGPRs and put 12 B of scratch into a form that had
+// none (profiles/r23b_fused_multirow_isa.txt).
+template <int GEOM>
+__device__ __forceinline__ bool qkv_multi(const SkinnyArgs& p) {
+  if constexpr (GEOM < 0) return p.seqs != 0;
+  else return GEOM == 1;
+}
+
+// EPI_QKV: the rotary position of GEMM row i.  One row per sequence: pos[i *
+// pos_sb].  Multi-row geometry: row i is token t = i / seqs of sequence m = i %
+// seqs, its position pos[m * pos_sb + t] of the [b, sq] ids as the decoders
+// hold them, clamped to the tables as kv_write_multi_k clamps it.
+template <int GEOM>
+__device__ __forceinline__ int64_t qkv_pos(const SkinnyArgs& p, int i) {
+  if (qkv_multi<GEOM>(p)) {
+    const int t = (i * p.seqs_mul) >> 16, m = i - t * p.seqs;
+    return min(max(p.pos[(int64_t)m * p.pos_sb + t], (int64_t)0), (int64_t)p.max_pos - 1);
+  }
+  return p.pos[(int64_t)i * p.pos_sb];
+}
+
+// EPI_QKV, multi-row geometry: the cache slot of GEMM row i (uniform: scalar
+// loads of the sequence's slot, key count and table entry, scalar arithmetic),
+// or -1 for a row that is not stored; col receives its cache column m.
+__device__ __forceinline__ int64_t multi_slot(const SkinnyArgs& p, int i, int& col) {
+  static_assert((KV_PAGE & (KV_PAGE - 1)) == 0, "page arithmetic by shift and mask");
+  const int t = (i * p.seqs_mul) >> 16, m = i - t * p.seqs;
+  col = m;
+  int64_t slot = p.slot_ptr[m * p.slot_sb] + t;
+  if (p.page_table && t > 0) {
+    const int sq = (p.M * p.seqs_mul) >> 16;
+    const int64_t lp = (int64_t)p.kv_len[m * p.kv_len_sb] - sq + t;  // (floor division, as torch's //)
+    const int64_t pi = min(max(lp >> __builtin_ctz(KV_PAGE), (int64_t)0), (int64_t)p.pt_ld - 1);
+    slot = (int64_t)p.page_table[(int64_t)m * p.pt_ld + pi] * KV_PAGE + (lp & (KV_PAGE - 1));
+  }
+  return slot >= 0 && slot < p.L ? slot : -1;
+}
+
+// EPI_QKV: the lane's 4 rotated k or v values (head h of group g, dims d ..
+// d + 3, feature n) to cache row `sl`, column `col`.  e4m3 cache: as rounded to
+// T, scaled, clamped (the convert alone turns an overflow into NaN), packed and
+// stored as one dword.
 template <typename T, int EPI>
+__device__ __forceinline__ void kv_put(const SkinnyArgs& p, const typename fa::MT<T>::x4& o, int h,
+                                       int n, int g, int d, int64_t sl, int col,
+                                       const EpiPre<T, EPI>& pre, bool use_pre) {
+  const int hd = p.hd;
+  if (p.kv_scale) {
+    const float inv = use_pre ? pre.kvr : kv_rscale(p, n);
+    float f[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) f[e] = fminf(fmaxf((float)o[e] * inv, -448.f), 448.f);
+    int w = 0;
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(f[0], f[1], w, false);
+    w = __builtin_amdgcn_cvt_pk_fp8_f32(f[2], f[3], w, true);
+    uint8_t* c8 = (uint8_t*)(h == p.r ? p.kcache : p.vcache);
+    *reinterpret_cast<int*>(c8 + sl * p.c_ss + (int64_t)col * p.c_sb + (int64_t)g * hd + d) = w;
+  } else {
+    T* cache = (T*)(h == p.r ? p.kcache : p.vcache);
+    *reinterpret_cast<typename fa::MT<T>::x4*>(cache + sl * p.c_ss + (int64_t)col * p.c_sb +
+                                               (int64_t)g * hd + d) = o;
+  }
+}
+
+template <typename T, int EPI, int GEOM = -1>
 __device__ __forceinline__ void epi_init(const SkinnyArgs& p, int lane, EpiPre<T, EPI>& e,
                                          int moff = 0) {
   if constexpr (EPI == EPI_QKV) {
     const int m = (lane & 15) + moff;
-    e.pos = m < p.M ? (int)p.pos[(int64_t)m * p.pos_sb] : 0;
+    e.pos = m < p.M ? (int)qkv_pos<GEOM>(p, m) : 0;
     const int64_t sl = p.slot_ptr ? *p.slot_ptr : p.slot;
     e.slot = (int64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(sl & 0xffffffffll)) |
              ((int64_t)__builtin_amdgcn_readfirstlane((int)(sl >> 32)) << 32);
@@ -167,7 +235,7 @@ __device__ __forceinline__ void epi_prefetch(const SkinnyArgs& p, int blk, int l
   }
 }
 
-template <typename T, int EPI, int ACT>
+template <typename T, int EPI, int ACT, int GEOM = -1>
 __device__ __forceinline__ void epilogue(const SkinnyArgs& p, int blk, const f4& t, int lane,
                                          int half, const EpiPre<T, EPI>& pre, bool use_pre,
                                          int moff = 0) {
@@ -207,7 +275,7 @@ __device__ __forceinline__ void epilogue(const SkinnyArgs& p, int blk, const f4&
     const int hd = p.hd, per_g = (p.r + 2) * hd;
     const int g = n / per_g, rem = n - g * per_g, h = rem / hd, d = rem - h * hd;
     if (h <= p.r) {  // q heads and the k head: rotate pairs (d, d+1), (d+2, d+3)
-      const int64_t pos = use_pre ? 0 : p.pos[(int64_t)m * p.pos_sb];
+      const int64_t pos = use_pre ? 0 : qkv_pos<GEOM>(p, m);
       const float* cr = p.cos + pos * (hd / 2) + d / 2;
       const float* sr = p.sin + pos * (hd / 2) + d / 2;
 #pragma unroll
@@ -222,6 +290,27 @@ __device__ __forceinline__ void epilogue(const SkinnyArgs& p, int blk, const f4&
     if (h < p.r) {
       dst = y + (int64_t)m * p.ldy + (int64_t)(g * p.r + h) * hd + d;
     } else {
+      if (qkv_multi<GEOM>(p)) {
+        // multi-row geometry (the verify step of the speculative decoders): the
+        // block's rows are tokens of several
+        // sequences and a sequence's rows straddle blocks, so the walk is the
+        // per-row one below, four rows' slots resolved per round on the scalar
+        // unit (multi_slot) before the lanes of each row store.
+        const int rows = min(16, M - moff);
+#pragma unroll 1
+        for (int i0 = 0; i0 < rows; i0 += 4) {
+          int64_t sl4[4];
+          int col4[4];
+#pragma unroll
+          for (int u = 0; u < 4; ++u) sl4[u] = multi_slot(p, moff + min(i0 + u, rows - 1), col4[u]);
+#pragma unroll
+          for (int u = 0; u < 4; ++u) {
+            if (m != moff + i0 + u || sl4[u] < 0) continue;
+            kv_put<T, EPI>(p, o, h, n, g, d, sl4[u], col4[u], pre, use_pre);
+          }
+        }
+        return;
+      }
       if (p.slot_sb) {
         // per-row slots (ragged decode; a wave-uniform branch): one pass per
         // row of the block, the row's slot a scalar load as in the scalar

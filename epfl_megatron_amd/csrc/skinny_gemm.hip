@@ -32,7 +32,10 @@
 //     (pairs 2i, 2i+1: inside one lane's 4 features), q goes to Y [M, nq*hd],
 //     k and v straight into the KV cache slot (device-resident slot index, so
 //     the step is graph-capturable; one index for the batch, or one per row
-//     with SkinnyArgs::slot_sb: ragged decode, inference/continuous.py).
+//     with SkinnyArgs::slot_sb: ragged decode, inference/continuous.py; or the
+//     multi-row geometry SkinnyArgs::seqs: 2..16 rows of each sequence, row t of
+//     sequence m at slot[m] + t or through the page table, the verify step of
+//     inference/speculative.py).
 // Shapes: M <= 32 (17-32 rows: two row blocks per W fragment in the
 // per-block kernel), N % 16 == 0, K % 128 == 0 (checked by the host).
 //
@@ -365,8 +368,10 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) 
 // W4 (MXFP4 weights): a ring slot is one 16-B piece and its scale dword = 4
 // k-steps; a full unit's slots are 1 KiB / 64 scale bytes apart, a half
 // unit's 512 B / 32.
+// MR: EPI_QKV with the multi-row geometry (SkinnyArgs::seqs) compiled in; the
+// forms without it hold no trace of it (qkv_multi, skinny_epi.h).
 template <typename T, bool NORM, int EPI, int ACT, int STEPS, int U, bool PACKED, int MB,
-          bool W8 = false, bool W4 = false>
+          bool W8 = false, bool W4 = false, bool MR = false>
 __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
   typedef typename fa::MT<T>::x8 x8;
   typedef std::conditional_t<W4, W4Slot, std::conditional_t<W8, i4, x8>> wslot;
@@ -467,7 +472,7 @@ __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
   if (wave == 0) {
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
-      epi_init<T, EPI>(p, lane, pre[mb], 16 * mb);
+      epi_init<T, EPI, MR ? 1 : 0>(p, lane, pre[mb], 16 * mb);
       epi_prefetch<T, EPI>(p, blk, lane, pre[mb], 16 * mb);
       if constexpr (W8) pre[mb].sc = epi_scale<EPI>(p, blk, half, lane);
     }
@@ -620,7 +625,7 @@ __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
 #pragma unroll
         for (int i = 1; i < WAVES; ++i) t += part[j & 1][i][mb][lane];  // fixed order
         if constexpr (W8) t = scale_tile(t, pre[mb].sc);
-        epilogue<T, EPI, ACT>(p, blk, t, lane, half, pre[mb], true, 16 * mb);
+        epilogue<T, EPI, ACT, MR ? 1 : 0>(p, blk, t, lane, half, pre[mb], true, 16 * mb);
       }
     }
     if (last) break;
@@ -659,6 +664,21 @@ int num_cus() {
 
 // STEPS = 0: one workgroup per output block (skinny_gemm_k); 16 / 32: the
 // persistent skinny_pgemm_k on min(blocks, CUs) workgroups.
+// one persistent form on g workgroups (all ten template arguments spelled out);
+// EPI_QKV calls with the multi-row geometry take the form compiled for it
+#define EMA_PG(g, ...)                                                                        \
+  do {                                                                                        \
+    if constexpr (EPI == EPI_QKV) {                                                           \
+      if (p.seqs) {                                                                           \
+        hipLaunchKernelGGL((skinny_pgemm_k<__VA_ARGS__, true>), dim3((unsigned)(g)), dim3(512), \
+                           0, s, p);                                                          \
+        break;                                                                                \
+      }                                                                                       \
+    }                                                                                         \
+    hipLaunchKernelGGL((skinny_pgemm_k<__VA_ARGS__, false>), dim3((unsigned)(g)), dim3(512), 0, \
+                       s, p);                                                                 \
+  } while (0)
+
 template <typename T, int WAVES, int STEPS, bool NORM, int EPI, int ACT>
 void launch(const SkinnyArgs& p, hipStream_t s) {
   const int nblocks = EPI == EPI_GLU ? p.N / 8 : p.N / 16;
@@ -679,12 +699,9 @@ void launch(const SkinnyArgs& p, hipStream_t s) {
         // call them)
         const int g = nblocks < num_cus() ? nblocks : num_cus();
         if (STEPS == 16 && p.M > 16)
-          hipLaunchKernelGGL((skinny_pgemm_k<T, NORM, EPI, ACT, STEPS, NORM ? 8 : STEPS, true,
-                                             STEPS == 16 ? 2 : 1, false, true>),
-                             dim3((unsigned)g), dim3(512), 0, s, p);
+          EMA_PG(g, T, NORM, EPI, ACT, STEPS, NORM ? 8 : STEPS, true, STEPS == 16 ? 2 : 1, false, true);
         else
-          hipLaunchKernelGGL((skinny_pgemm_k<T, NORM, EPI, ACT, STEPS, STEPS, true, 1, false, true>),
-                             dim3((unsigned)g), dim3(512), 0, s, p);
+          EMA_PG(g, T, NORM, EPI, ACT, STEPS, STEPS, true, 1, false, true);
       }
       return;
     }
@@ -701,11 +718,9 @@ void launch(const SkinnyArgs& p, hipStream_t s) {
         // 8-deep 16-bit forms, the whole block of a K = 4096 stream
         const int g = nblocks < num_cus() ? nblocks : num_cus();
         if (STEPS == 16 && p.M > 16)
-          hipLaunchKernelGGL((skinny_pgemm_k<T, NORM, EPI, ACT, STEPS, 16, true, STEPS == 16 ? 2 : 1, true>),
-                             dim3((unsigned)g), dim3(512), 0, s, p);
+          EMA_PG(g, T, NORM, EPI, ACT, STEPS, 16, true, STEPS == 16 ? 2 : 1, true, false);
         else
-          hipLaunchKernelGGL((skinny_pgemm_k<T, NORM, EPI, ACT, STEPS, 16, true, 1, true>),
-                             dim3((unsigned)g), dim3(512), 0, s, p);
+          EMA_PG(g, T, NORM, EPI, ACT, STEPS, 16, true, 1, true, false);
       }
       return;
     }
@@ -744,22 +759,19 @@ void launch(const SkinnyArgs& p, hipStream_t s) {
       // 14.5 vs 13.0 / 14.3 us at 24 / 32 rows, profiles/r4as_pskinny_u16.txt)
       if (p.M > 16) {
         if (p.packed)
-          hipLaunchKernelGGL((skinny_pgemm_k<T, NORM, EPI, ACT, STEPS, 8, true, 2>), dim3((unsigned)g),
-                             dim3(512), 0, s, p);
+          EMA_PG(g, T, NORM, EPI, ACT, STEPS, 8, true, 2, false, false);
         else
-          hipLaunchKernelGGL((skinny_pgemm_k<T, NORM, EPI, ACT, STEPS, 8, false, 2>), dim3((unsigned)g),
-                             dim3(512), 0, s, p);
+          EMA_PG(g, T, NORM, EPI, ACT, STEPS, 8, false, 2, false, false);
         return;
       }
     }
     if (p.packed)
-      hipLaunchKernelGGL((skinny_pgemm_k<T, NORM, EPI, ACT, STEPS, U, true, 1>), dim3((unsigned)g),
-                         dim3(512), 0, s, p);
+      EMA_PG(g, T, NORM, EPI, ACT, STEPS, U, true, 1, false, false);
     else
-      hipLaunchKernelGGL((skinny_pgemm_k<T, NORM, EPI, ACT, STEPS, U, false, 1>), dim3((unsigned)g),
-                         dim3(512), 0, s, p);
+      EMA_PG(g, T, NORM, EPI, ACT, STEPS, U, false, 1, false, false);
   }
 }
+#undef EMA_PG
 
 template <typename T, int WAVES, int STEPS>
 void dispatch(const SkinnyArgs& p, int epi, hipStream_t s) {

@@ -18,12 +18,16 @@ The cells that exist, by ``step_kind`` (``LayerKV._check`` refuses the rest):
   t`` (the slot of each sequence's first new row, one value or one per row;
   paged: physical, and the later rows through the table) and
   ``flash_decode_cached`` reads ``ip.device_kv_len`` keys, the count after the
-  ``sq`` rows.  No host value is read.  Not with the fused decode layer, not
-  with FP8 calibration.  On the GPU (bf16 / fp16, head dim 64 / 128) RoPE and
-  the write are one launch, ``write_multi_native`` (``csrc/kv_write_multi.hip``);
-  elsewhere the layer's RoPE pass and ``_write_multi`` in torch.  Callers: the
-  speculative decoders (``inference/speculative.py``), whose verify step is
-  this cell.
+  ``sq`` rows.  No host value is read.  Not with FP8 calibration.  On the GPU
+  (bf16 / fp16, head dim 64 / 128) RoPE and the write are one launch,
+  ``write_multi_native`` (``csrc/kv_write_multi.hip``); elsewhere the layer's
+  RoPE pass and ``_write_multi`` in torch.  Callers: the speculative decoders
+  (``inference/speculative.py``), whose verify step is this cell.
+- the same step through the fused decode layer (opt-in: ``ip.device_multi ==
+  "fused"``; any other truthy value keeps the unfused layer, and ``fused=True``
+  is refused under it): the layer's QKV epilogue stores the ``sq * b`` rows by
+  the same rules (``SkinnyArgs::seqs``, ``csrc/skinny_epi.h``) and
+  ``decode_multi`` reads them.
 - eager decode step: host slot ``s0``.  Not paged.
 - restart prefill: host slot 0; attends over the fresh K / V (16-bit columns:
   over the cached rows).  Paged: one row, scattered by its table.
@@ -34,7 +38,8 @@ The FP8 kernels of the unfused layer need the GPU, head dim 64 or 128 and
 ``--use_flash_attn``; else the keys in hand are gathered / dequantised for
 ``flash_attn_func`` or the layer's core attention.  The fused decode layer
 (``models/transformer.py``) stores the new row in its QKV epilogue: it takes
-``kc``, ``vc``, ``slot_t``, ``slot``, ``scales`` and calls ``decode``.
+``kc``, ``vc``, ``slot_t``, ``slot``, ``scales`` and calls ``decode``
+(``decode_multi`` in the multi-row cell).
 """
 import os
 
@@ -138,9 +143,10 @@ class LayerKV:
             raise NotImplementedError("hipGraph decode needs the native decode attention "
                                       "kernel (GPU, bf16/fp16, head_dim 64 or 128)")
         if kind == DEVICE_MULTI:
-            if fused:
-                raise NotImplementedError("the fused decode layer is single-row: a multi-row "
-                                          "device step (device_multi) runs the unfused layer")
+            if fused and ip.device_multi != "fused":
+                raise NotImplementedError("the fused decode layer takes a multi-row device step "
+                                          "only under device_multi = \"fused\": any other value "
+                                          "runs the unfused layer")
             if self.fp8 and FP8_KV_CALIBRATE:
                 raise NotImplementedError("a multi-row device step does not calibrate the FP8 KV "
                                           "scales (--inference_fp8_kv_calibrate)")
@@ -311,6 +317,23 @@ class LayerKV:
             return flash_decode_cached(q, keys, vals, None, window=window(n), kv_scale=sc)
         return flash_attn_func(q, keys, vals, causal=True, window=window(n))
 
+    def decode_multi(self, q, window, rows_first=True):
+        """Attention of the multi-row device step, ``q [b, sq, np, hd]`` (any
+        strides with ``hd`` contiguous: the fused layer passes its ``[sq * b,
+        np * hd]`` projection as a view) over the cache with the ``sq`` new
+        rows of every sequence in it.  ``rows_first``: the result ``[b, sq, np,
+        hd]`` lies in memory in ``[sq, b]`` row order, as the fused layer's next
+        product reads it."""
+        ip = self.ip
+        if self.paged:
+            return flash_decode_cached(q, self.kmem.transpose(0, 1), self.vmem.transpose(0, 1),
+                                       ip.device_kv_len, window=window(ip.max_sequence_len),
+                                       kv_scale=self.scales, page_table=self.table,
+                                       capacity=ip.max_sequence_len, rows_first=rows_first)
+        return flash_decode_cached(q, self.kc.transpose(0, 1), self.vc.transpose(0, 1),
+                                   ip.device_kv_len, window=window(self.kc.shape[0]),
+                                   kv_scale=self.scales, rows_first=rows_first)
+
     def attend(self, q, k, v, window, flash, core):
         """The unfused layer's attention after ``write(k, v)``: ``q [sq, b, np,
         hd]`` -> ``[sq, b, np * hd]``.  ``flash``: the layer's ``use_flash_attn``;
@@ -321,16 +344,7 @@ class LayerKV:
         qt = q.transpose(0, 1)
         fp8_native = self.fp8 and self.native and flash
         if self.kind == DEVICE_MULTI:
-            ip = self.ip
-            if self.paged:
-                o = flash_decode_cached(qt, self.kmem.transpose(0, 1), self.vmem.transpose(0, 1),
-                                        ip.device_kv_len, window=window(ip.max_sequence_len),
-                                        kv_scale=sc, page_table=self.table,
-                                        capacity=ip.max_sequence_len)
-            else:
-                o = flash_decode_cached(qt, self.kc.transpose(0, 1), self.vc.transpose(0, 1),
-                                        ip.device_kv_len, window=window(self.kc.shape[0]),
-                                        kv_scale=sc)
+            o = self.decode_multi(qt, window, rows_first=False)
         elif self.kind == DEVICE_DECODE or (sq == 1 and fp8_native):
             o = self.decode(qt, window)
         elif self.paged and s0 > 0 and flash:  # continued: the first s0 keys are in the pages only

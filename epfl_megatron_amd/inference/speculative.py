@@ -21,11 +21,18 @@ never covers a row before it is rewritten.
 No draft model, no second graph, no host work per step: every quantity the
 step depends on is a device tensor (``spec_tail_k``'s comment lists them).
 
-Not built: the fused decode layer at more than one row per sequence (a step
-here runs the unfused layer, so a step costs more than a lockstep greedy
-step; speculation pays only when drafts are accepted), a draft model, tree
-drafts, the continuous batcher and paged caches, the text-generation API /
-server flag, sampling settings per row.
+``fused=True`` (opt-in) runs the verify step through the fused decode layer
+instead (``ip.device_multi = "fused"``: the ``batch * rows`` rows take the
+weight-streaming GEMMs of ``csrc/skinny_gemm.hip`` / ``csrc/wide_gemm.hip``,
+whose QKV epilogue rotates and stores every row by the multi-row cell's rules,
+and the e4m3 / MXFP4 weight packs of ``--inference_fp8_weights`` /
+``--inference_mxfp4_weights``).  It needs ``batch * rows`` <= 32 (64 where
+the wide kernel is on); steps above that, and layers the fused decode layer
+does not take, run the unfused layer as without it.
+
+Not built: a draft model, tree drafts, the continuous batcher and paged
+caches, the text-generation API / server flag, sampling settings per row, the
+fused verify step as the default.
 
 ``SpeculativeSamplingDecoder`` is the same loop for sampled requests: its tail
 (``spec_sample_tail_k``) draws every row with ``sample_tail_k``'s draw and
@@ -124,9 +131,16 @@ class SpeculativeGreedyDecoder:
     same ``ip`` must clear it again); ``next_tokens`` is the greedy choice from
     its logits.  Every row generates ``max_new_tokens`` tokens after
     ``next_tokens`` unless it commits ``stop_id`` first.  ``graph=False`` runs
-    the same step eagerly (on the CPU with ``spec_tail_ref``)."""
+    the same step eagerly (on the CPU with ``spec_tail_ref``).  ``fused=True``:
+    the verify step through the fused decode layer (module docstring; off by
+    default).  Measured (``profiles/r23a_spec_fused.txt``, Llama-2-7B shapes) a
+    replay takes 2.98 against 3.50 ms at 4 rows and 4.96 against 5.05 ms at 32
+    in bf16, 1.83 against 3.49 and 3.85 against 5.05 ms under MXFP4; it loses
+    in one cell, ``batch * rows`` = 64 under MXFP4 (6.77 against 5.59 ms: the
+    wide kernel), which a default should exclude."""
 
-    def __init__(self, model, inference_params, batch, max_new_tokens, rows=4, ngram=3, graph=True):
+    def __init__(self, model, inference_params, batch, max_new_tokens, rows=4, ngram=3, graph=True,
+                 fused=False):
         if state.model_parallel_is_initialized() and \
                 state.get_pipeline_model_parallel_world_size() > 1:
             raise NotImplementedError("the speculative decode loop needs the whole model (PP = 1)")
@@ -142,6 +156,7 @@ class SpeculativeGreedyDecoder:
             raise RuntimeError("hipGraph decode needs a GPU")
         self.model, self.ip, self.batch = model, inference_params, batch
         self.max_new, self.rows, self.ngram, self.graph_mode = max_new_tokens, rows, ngram, graph
+        self.fused = fused
         self.dev = torch.device("cuda", torch.cuda.current_device()) if graph else \
             next(model.parameters()).device
         self.graph = None
@@ -223,7 +238,8 @@ class SpeculativeGreedyDecoder:
             self.tick.zero_()
             self.active.fill_(1)
             self.ctl[:3].copy_(torch.tensor([stop_id, self.ngram, b]))
-            ip.device_offset, ip.device_kv_len, ip.device_multi = self.slot, self.kv_len, True
+            ip.device_offset, ip.device_kv_len = self.slot, self.kv_len
+            ip.device_multi = "fused" if self.fused else True
             if self.graph_mode and self.graph is None:
                 self._capture()
 
@@ -289,11 +305,12 @@ class SpeculativeSamplingDecoder(SpeculativeGreedyDecoder):
     ``fctl``): a later ``start()`` with others replays the same graph.
     ``start()`` takes ``(seed, offset0)`` from the CUDA generator (TP rank 0's)
     and advances it past the generation, or from ``seed_offset``.  ``graph=False``
-    runs eagerly (on the CPU with ``spec_sample_tail_ref``)."""
+    runs eagerly (on the CPU with ``spec_sample_tail_ref``); ``fused`` as in
+    ``SpeculativeGreedyDecoder``."""
 
     def __init__(self, model, inference_params, batch, max_new_tokens, rows=4, ngram=3, graph=True,
-                 vocab_size=None):
-        super().__init__(model, inference_params, batch, max_new_tokens, rows, ngram, graph)
+                 vocab_size=None, fused=False):
+        super().__init__(model, inference_params, batch, max_new_tokens, rows, ngram, graph, fused)
         self.vocab_size = vocab_size
         self.seed = self.offset0 = None
 

@@ -50,7 +50,10 @@ from .utils import attention_mask_func, erf_gelu
 # layer as 5 weight-streaming launches with the elementwise work fused in
 # (csrc/skinny_gemm.hip): [RMSNorm + QKV + RoPE + KV-cache write] ->
 # decode attention -> [dense + residual] -> [RMSNorm + fc1 + GLU] ->
-# [fc2 + residual].  EMA_DECODE_FUSED=0 keeps the unfused kernels.
+# [fc2 + residual].  EMA_DECODE_FUSED=0 keeps the unfused kernels.  The
+# multi-row device step (2..16 rows per sequence, the speculative decoders'
+# verify step) takes the same five launches on its sq * b rows under
+# ip.device_multi = "fused" (inference/kv_cache.py); otherwise it runs unfused.
 _DECODE_FUSED = os.environ.get("EMA_DECODE_FUSED", "1") != "0"
 # 33-64 rows can run the same fused step through csrc/wide_gemm.hip (X staged
 # in LDS).  EMA_WIDE_GEMM: "auto" (default) takes it under the quantised-weight
@@ -506,15 +509,28 @@ class ParallelTransformerLayer(MegatronModule):
                 and (self.hidden_dropout == 0.0 or not self.training) and self.drop_path is None
                 and hasattr(self.input_layernorm, "forward_residual"))
 
-    def _decode_fused_ok(self, hidden_states, ip):
+    def _decode_fused_ok(self, hidden_states, ip, position_ids=None):
         """One decode step of a plain pre-RMSNorm rotary GLU block (any TP size,
-        no sequence parallelism: a decode step has one row per sequence)."""
+        no sequence parallelism: a decode step has one row per sequence), or
+        the multi-row device step under ``ip.device_multi == "fused"``
+        (``inference/kv_cache.py``): ``sq`` in 2..16 rows per sequence with
+        ``[b, sq]`` position ids, which runs the same kernels on ``sq * b`` rows."""
         if not (_DECODE_FUSED and ip is not None and not torch.is_grad_enabled()
                 and hidden_states.is_cuda and hidden_states.dim() == 3
-                and hidden_states.shape[0] == 1
-                and hidden_states.shape[1] <= (64 if _wide_on() else 32)
+                and hidden_states.shape[0] * hidden_states.shape[1] <= (64 if _wide_on() else 32)
                 and hidden_states.dtype in (torch.bfloat16, torch.float16)
                 and self._fused_residual_ok()):
+            return False
+        nt, b = hidden_states.shape[:2]
+        if nt != 1 and not (
+                2 <= nt <= 16 and getattr(ip, "device_multi", False) == "fused"
+                and kv_cache.step_kind(ip, nt) == kv_cache.DEVICE_MULTI
+                and position_ids is not None and tuple(position_ids.shape) == (b, nt)
+                and position_ids.dtype == torch.long and position_ids.is_contiguous()
+                and ip.device_offset.dtype == torch.long and ip.device_offset.is_contiguous()
+                and (ip.page_table is None or (ip.device_kv_len.dtype == torch.int32
+                                               and ip.device_kv_len.is_contiguous()
+                                               and ip.page_table.dtype == torch.int32))):
             return False
         sa, mlp = self.self_attention, self.mlp
         if not (isinstance(self.input_layernorm, RMSNorm)
@@ -528,7 +544,7 @@ class ParallelTransformerLayer(MegatronModule):
                 and sa.hidden_size_per_attention_head in (64, 128)):
             return False
         C = ext()
-        b, H = hidden_states.shape[1], hidden_states.shape[2]
+        b, H = nt * b, hidden_states.shape[2]  # the rows of every product
         wq, wo = sa.query_key_value.weight, sa.dense.weight
         w1, w2 = mlp.dense_h_to_4h.weight, mlp.dense_4h_to_h.weight
         ws = (wq, wo, w1, w2, self.input_layernorm.weight, self.post_attention_layernorm.weight)
@@ -551,16 +567,26 @@ class ParallelTransformerLayer(MegatronModule):
         sa, mlp = self.self_attention, self.mlp
         ln1, ln2 = self.input_layernorm, self.post_attention_layernorm
         C = ext()
-        _, b, H = hidden_states.shape
+        # nt rows per sequence: 1, or the 2..16 of the multi-row device step,
+        # whose nt * b rows (row t * b + m: token t of sequence m) run through
+        # the same five launches; b is the row count of every product from here
+        nt, nseq, H = hidden_states.shape
+        b = nt * nseq
         x = hidden_states.reshape(b, H)
         if not x.is_contiguous():
             x = x.contiguous()
-        # the cache operands of the QKV epilogue, which writes the new row (and
-        # quantises it for an FP8 cache)
+        # the cache operands of the QKV epilogue, which writes the new rows (and
+        # quantises them for an FP8 cache)
         ng, r, hd = sa.num_groups_per_partition, sa.q_per_group, sa.hidden_size_per_attention_head
-        kv = LayerKV(ip, sa.layer_number, ng, hd, sa.params_dtype, x.device, 1, b, fused=True)
+        kv = LayerKV(ip, sa.layer_number, ng, hd, sa.params_dtype, x.device, nt, nseq, fused=True)
         cos, sin = sa._rope(x.device)
-        if position_ids is None:
+        # multi-row: the epilogue reads the [nseq, nt] ids, the slots, the key
+        # counts and the page table as the decoders hold them (SkinnyArgs::seqs)
+        multi = () if nt == 1 else (nseq, ip.device_kv_len if kv.paged else None,
+                                    kv.table if kv.paged else None)
+        if nt > 1:
+            pos = position_ids
+        elif position_ids is None:
             pos = torch.full((b, 1), ip.sequence_len_offset, dtype=torch.long,
                              device=x.device)
         else:
@@ -596,14 +622,23 @@ class ParallelTransformerLayer(MegatronModule):
         xq = rms_norm(x, ln1.weight, ln1.eps) if sep else x
         if wide:
             q = C.wide_qkv_rope_cache(xq, pq, ng, r, hd, cos, sin, pos, kv.kc, kv.vc,
-                                      kv.slot_t, kv.slot, sq, kv.scales)
+                                      kv.slot_t, kv.slot, sq, kv.scales,
+                                      *((0, *multi) if multi else ()))  # (0: the host's split)
+        elif multi:
+            q = C.skinny_qkv_rope_cache(xq, wq if pq is None else pq, None if sep else ln1.weight,
+                                        ln1.eps, ng, r, hd, cos, sin, pos, kv.kc, kv.vc, kv.slot_t,
+                                        kv.slot, pq is not None, sq, kv.scales, *multi)
         else:
             q = C.skinny_qkv_rope_cache(xq, wq if pq is None else pq, None if sep else ln1.weight,
                                         ln1.eps, ng, r, hd,
                                         cos, sin, pos, kv.kc, kv.vc, kv.slot_t, kv.slot,
                                         pq is not None, sq,
                                         *(() if kv.scales is None else (kv.scales,)))
-        o = kv.decode(q.view(b, 1, ng * r, hd), sa._window)
+        if multi:  # q and o stay in [nt, nseq] row order: strided views, no copies
+            o = kv.decode_multi(q.view(nt, nseq, ng * r, hd).transpose(0, 1),
+                                sa._window).transpose(0, 1)
+        else:
+            o = kv.decode(q.view(b, 1, ng * r, hd), sa._window)
         # Row-parallel dense / fc2 under TP: each rank's product is a partial
         # sum; TP rank 0 alone adds the residual in its epilogue, so one
         # all-reduce of [b, H] yields partial sums + residual (reference
@@ -619,7 +654,7 @@ class ParallelTransformerLayer(MegatronModule):
                            tp.layers._GLU_KIND[mlp.glu_activation], s1)
             h3 = C.wide_gemm(y, p2, h2 if first else None, s2)
             h3 = tp.reduce_from_tensor_model_parallel_region(h3)
-            return h3.view(1, b, H)
+            return h3.view(nt, nseq, H)
         h2 = C.skinny_norm_gemm(o.reshape(b, -1), wo if po is None else po, None, 0.0,
                                 x if first else None, po is not None, so)
         h2 = tp.reduce_from_tensor_model_parallel_region(h2)
@@ -629,7 +664,7 @@ class ParallelTransformerLayer(MegatronModule):
         h3 = C.skinny_norm_gemm(y, w2 if p2 is None else p2, None, 0.0, h2 if first else None,
                                 p2 is not None, s2)
         h3 = tp.reduce_from_tensor_model_parallel_region(h3)
-        return h3.view(1, b, H)
+        return h3.view(nt, nseq, H)
 
     def _forward_fused_residual(self, hidden_states, attention_mask, inference_params,
                                 position_ids):
@@ -656,7 +691,7 @@ class ParallelTransformerLayer(MegatronModule):
 
     def _forward(self, hidden_states, attention_mask, encoder_output=None, enc_dec_attn_mask=None,
                  inference_params=None, position_ids=None):
-        if self._decode_fused_ok(hidden_states, inference_params):
+        if self._decode_fused_ok(hidden_states, inference_params, position_ids):
             return self._forward_decode_fused(hidden_states, inference_params, position_ids)
         if self._fused_residual_ok():
             return self._forward_fused_residual(hidden_states, attention_mask, inference_params,

@@ -174,7 +174,8 @@ def _flash_decode(q, k, v, scale, kv_len=None, window=0, kv_scale=None, page_tab
     return out
 
 
-def _decode_cached_mq(q, k, v, kv_len, softmax_scale, window, kv_scale, page_table, capacity):
+def _decode_cached_mq(q, k, v, kv_len, softmax_scale, window, kv_scale, page_table, capacity,
+                      rows_first=False):
     """``flash_decode_cached`` for 2..16 query rows per sequence (its mask)."""
     b, sq, nq, d = q.shape
     nkv = k.shape[2]
@@ -190,7 +191,10 @@ def _decode_cached_mq(q, k, v, kv_len, softmax_scale, window, kv_scale, page_tab
     else:
         capacity = k.shape[1]
     if use_native(q) and d in (64, 128) and q.dtype in (torch.bfloat16, torch.float16):
-        out = torch.empty(b, sq, nq, d, dtype=q.dtype, device=q.device)
+        if rows_first:  # the kernel stores through o_sb / o_ss: no copy either way
+            out = torch.empty(sq, b, nq, d, dtype=q.dtype, device=q.device).transpose(0, 1)
+        else:
+            out = torch.empty(b, sq, nq, d, dtype=q.dtype, device=q.device)
         ext().flash_decode_mq(q, k, v, out, b, sq, int(capacity), nq, nkv, d,
                               list(_bsnd_strides(q, nq // nkv)), list(_bsnd_strides(k, 1)[:3]),
                               list(_bsnd_strides(v, 1)[:3]),
@@ -223,7 +227,7 @@ def _decode_cached_mq(q, k, v, kv_len, softmax_scale, window, kv_scale, page_tab
 
 
 def flash_decode_cached(q, k, v, kv_len, softmax_scale=None, window=0, kv_scale=None,
-                        page_table=None, capacity=None):
+                        page_table=None, capacity=None, rows_first=False):
     """One query row per sequence (or 2..16, below) against a whole KV cache ``k / v [b, smax,
     nkv, d]`` of which the first ``kv_len`` (device int32) keys are valid
     (with ``window``: the last ``window`` of those).  ``kv_len`` None: all
@@ -243,8 +247,10 @@ def flash_decode_cached(q, k, v, kv_len, softmax_scale=None, window=0, kv_scale=
     The ``sq`` new rows are already in the cache and ``kv_len`` counts them:
     with ``n_i`` keys in row ``i`` and ``e = n_i - (sq - 1 - t)``, query token
     ``t`` sees key ``j`` iff ``j < e`` and (``window == 0`` or ``j >= e -
-    window``); a token with ``e <= 0`` gives zeros.  More rows than 16 are a
-    prefill: ``flash_attn_func`` / ``flash_attn_paged``."""
+    window``); a token with ``e <= 0`` gives zeros.  ``rows_first``: the
+    result ``[b, sq, nq, d]`` is a view of memory in ``[sq, b]`` row order (the
+    fused decode layer's), written in place by the kernel.  More rows than 16
+    are a prefill: ``flash_attn_func`` / ``flash_attn_paged``."""
     _check_window(window, True)
     sq = q.shape[1]
     if sq > 16:
@@ -252,7 +258,7 @@ def flash_decode_cached(q, k, v, kv_len, softmax_scale=None, window=0, kv_scale=
                          "use flash_attn_func (flash_attn_paged on a pool) for a prefill")
     if sq > 1:
         return _decode_cached_mq(q, k, v, kv_len, softmax_scale, window, kv_scale, page_table,
-                                 capacity)
+                                 capacity, rows_first)
     if page_table is not None:
         from ..inference.paged import KV_PAGE, gather_rows
         if kv_len is None:

@@ -47,6 +47,9 @@ repetitions each, alternating, once on a prompt of period 8 and once on a random
 one; reports tokens/s, ms per replay and the mean accepted drafts per step.
 With --top_k / --top_p / --temperature: SpeculativeSamplingDecoder against
 GraphedSamplingDecoder, both started from the same generator state.
+--fused_verify adds, in the same alternation, the speculative decoder with
+fused=True (the verify step through the fused decode layer) and the lockstep
+decoder on batch * S sequences, the floor a verify step of as many rows can approach.
 
 Usage: python scripts/serve_bench.py [--batches 1,8,32] [--graph [--speculative S [--ngram G]]]
        [--top_k K | --top_p P] [--temperature T]
@@ -122,6 +125,9 @@ def main():
                     help="--graph: rows per sequence of SpeculativeGreedyDecoder, or with --top_k / "
                          "--top_p / --temperature SpeculativeSamplingDecoder (2..16; 0: off)")
     ap.add_argument("--ngram", type=int, default=3, help="--speculative: longest n-gram looked up")
+    ap.add_argument("--fused_verify", action="store_true",
+                    help="--speculative: also time the decoder with fused=True (the verify step through "
+                         "the fused decode layer) and the lockstep decoder on batch * S rows, alternating")
     ap.add_argument("--torch_front", action="store_true",
                     help="--speculative: also time the decoder captured with the multi-row step's RoPE "
                          "and cache write in torch (kv_cache.WRITE_MULTI_NATIVE off), alternating")
@@ -469,27 +475,40 @@ def speculative(a, m, sampling, skw):
                    "random": torch.randint(0, 32000, (B, a.prompt + 8), generator=g)}
         for kind, prompt in prompts.items():
             prompt = prompt[:, :a.prompt].cuda()
-            decs, secs, replays = {}, {"greedy": [], "speculative": []}, 0
+            decs, secs, replays = {}, {"greedy": [], "speculative": []}, {}
             if a.torch_front:  # the same decoder captured with RoPE + _write_multi in torch
                 secs["speculative_torch_front"] = []
+            if a.fused_verify:
+                # the verify step through the fused decode layer, and the floor it can
+                # approach: the lockstep decoder on as many rows (B * S sequences)
+                secs["speculative_fused"], secs["greedy_rows"] = [], []
             with torch.no_grad():
                 for name in secs:
-                    ip = InferenceParams(B, total)
-                    nxt = m(prompt, pos, None, inference_params=ip)[:, -1].argmax(-1)
+                    nb = B * S if name == "greedy_rows" else B
+                    ip = InferenceParams(nb, total)
+                    first = m(prompt.repeat(nb // B, 1), pos.repeat(nb // B, 1), None,
+                              inference_params=ip)[:, -1].argmax(-1)
                     ip.sequence_len_offset = a.prompt
+                    if name == "greedy_rows":
+                        decs[name], nxt_rows = lock(m, ip, nb, a.gen, **kw), first
+                        continue
+                    nxt = first
                     decs[name] = lock(m, ip, B, a.gen, **kw) if name == "greedy" else \
-                        spec_cls(m, ip, B, a.gen, rows=S, ngram=a.ngram, **kw)
+                        spec_cls(m, ip, B, a.gen, rows=S, ngram=a.ngram,
+                                 fused=name == "speculative_fused", **kw)
                 for rep in range(a.reps + 1):  # rep 0: capture and warm-up
                     for name, dec in decs.items():
                         torch.cuda.manual_seed(a.seed)
                         kv_cache.WRITE_MULTI_NATIVE = name != "speculative_torch_front"  # (read at capture)
                         if name == "greedy":
                             dec.start(nxt.view(B, 1), a.prompt, **skw)
+                        elif name == "greedy_rows":
+                            dec.start(nxt_rows.view(B * S, 1), a.prompt, **skw)
                         else:
                             dec.start(prompt, nxt, **skw)
 
                         def run():
-                            if name == "greedy":
+                            if name.startswith("greedy"):
                                 for _ in range(a.gen):
                                     dec.step()
                                 return a.gen
@@ -500,20 +519,27 @@ def speculative(a, m, sampling, skw):
                         n, dt = _timed(run)
                         if rep:
                             secs[name].append(round(dt, 4))
-                            replays = n if name == "speculative" else replays
+                            replays[name] = n
             kv_cache.WRITE_MULTI_NATIVE = True
             spec = decs["speculative"]
             toks, lens = spec.generated()
             r = {"mode": "speculative", "sampling": dict(skw) if sampling else None, "batch": B,
                  "rows": S, "ngram": a.ngram, "prompt_kind": kind,
                  "prompt": a.prompt, "gen": a.gen, "mean_accepted": round(spec.mean_accepted(), 3),
-                 "speculative_replays": replays,
+                 "speculative_replays": replays["speculative"],
                  "same_tokens": bool(lens.eq(a.gen).all()) and
                  torch.equal(toks, decs["greedy"].history[:, :a.gen])}
+            if a.fused_verify:
+                ftoks, flens = decs["speculative_fused"].generated()
+                r["fused_replays"] = replays["speculative_fused"]
+                r["fused_mean_accepted"] = round(decs["speculative_fused"].mean_accepted(), 3)
+                r["fused_same_tokens"] = bool(flens.eq(a.gen).all()) and \
+                    torch.equal(ftoks, decs["greedy"].history[:, :a.gen])
             for name, t in secs.items():
-                n = a.gen if name == "greedy" else replays
+                n = replays[name]
                 r[name + "_seconds"] = t
-                r[name + "_tokens_per_s"] = [round(B * a.gen / x, 1) for x in t]
+                if name != "greedy_rows":  # (B * S sequences: not this row's tokens)
+                    r[name + "_tokens_per_s"] = [round(B * a.gen / x, 1) for x in t]
                 r[name + "_ms_per_replay"] = [round(1e3 * x / n, 3) for x in t]
             print(json.dumps(r), flush=True)
             res.append(r)
