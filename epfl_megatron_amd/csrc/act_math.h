@@ -40,6 +40,13 @@ __device__ __forceinline__ float dact(float x) {
   }
 }
 
+// GeLU (tanh approximation / exact erf): gelu_fwd_k and the decode GEMMs'
+// activation epilogue (skinny_epi.h EPI_ACT) run these same functions
+__device__ __forceinline__ float gelu_tanh(float z) {
+  return z * 0.5f * (1.f + tanhf(0.79788456f * z * (1.f + 0.044715f * z * z)));
+}
+__device__ __forceinline__ float gelu_erf(float z) { return 0.5f * z * (1.f + erff(z * kInvSqrt2)); }
+
 // act(x) and act'(x) together, sharing one sigmoid (SwiGLU: act = x s,
 // act' = s (1 + x (1 - s)) = s + act (1 - s)).
 template <int KIND>

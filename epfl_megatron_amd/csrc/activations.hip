@@ -57,14 +57,11 @@ __global__ __launch_bounds__(256) void glu_bwd_k(const T* __restrict__ dy, const
   st16(dr + F + c, dg);
 }
 
-__device__ __forceinline__ float gelu_tanh(float z) {
-  return z * 0.5f * (1.f + tanhf(0.79788456f * z * (1.f + 0.044715f * z * z)));
-}
+// (gelu_tanh / gelu_erf: act_math.h)
 __device__ __forceinline__ float dgelu_tanh(float z) {
   const float t = tanhf(0.79788456f * z * (1.f + 0.044715f * z * z));
   return 0.5f * z * ((1.f - t * t) * (0.79788456f + 0.1070322243f * z * z)) + 0.5f * (1.f + t);
 }
-__device__ __forceinline__ float gelu_erf(float z) { return 0.5f * z * (1.f + erff(z * kInvSqrt2)); }
 __device__ __forceinline__ float dgelu_erf(float z) {
   return 0.5f * (1.f + erff(z * kInvSqrt2)) + z * kInvSqrt2Pi * __expf(-0.5f * z * z);
 }

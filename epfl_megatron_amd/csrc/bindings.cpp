@@ -820,7 +820,8 @@ at::Tensor skinny_gemm(const at::Tensor& x, const at::Tensor& w, bool packed,
 // 3 QKV (-> q [M, nq * hd]; k / v written into the cache slot).
 static ema::SkinnyArgs skinny_args(const at::Tensor& x, const at::Tensor& w,
                                    const c10::optional<at::Tensor>& norm_w, double eps,
-                                   bool packed, const c10::optional<at::Tensor>& w_scale) {
+                                   bool packed, const c10::optional<at::Tensor>& w_scale,
+                                   const c10::optional<at::Tensor>& norm_b = c10::nullopt) {
   check_gpu(x, "x");
   const bool mx = skinny_is_mxfp4(w_scale);
   TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.size(1) == (mx ? 2 : 1) * w.size(1),
@@ -846,21 +847,38 @@ static ema::SkinnyArgs skinny_args(const at::Tensor& x, const at::Tensor& w,
     p.norm_w = norm_w->data_ptr();
     p.eps = (float)eps;
   }
+  if (norm_b) {  // LayerNorm prologue: gamma and beta, one row block
+    TORCH_CHECK(norm_w && norm_b->is_cuda() && norm_b->is_contiguous() && norm_b->numel() == p.K &&
+                norm_b->scalar_type() == x.scalar_type() && p.M <= 16,
+                "skinny: a LayerNorm prologue needs norm_w, norm_b [K] of the x dtype and M <= 16");
+    p.norm_b = norm_b->data_ptr();
+  }
   return p;
 }
 
+static at::Tensor wide_out(const at::Tensor& x, const c10::optional<at::Tensor>& out, int64_t M,
+                           int64_t N);
+
+// norm_b: norm_w / norm_b are a LayerNorm's gamma / beta (plain and GeLU
+// epilogues); gelu: the erf-GeLU epilogue (un-normed or LayerNorm forms); out:
+// the rows to write (wide_out), e.g. a column range of a wider buffer
 at::Tensor skinny_norm_gemm(const at::Tensor& x, const at::Tensor& w,
                             const c10::optional<at::Tensor>& norm_w, double eps,
                             const c10::optional<at::Tensor>& res, bool packed,
-                            const c10::optional<at::Tensor>& w_scale) {
-  auto p = skinny_args(x, w, norm_w, eps, packed, w_scale);
+                            const c10::optional<at::Tensor>& w_scale,
+                            const c10::optional<at::Tensor>& norm_b, bool gelu,
+                            const c10::optional<at::Tensor>& out) {
+  auto p = skinny_args(x, w, norm_w, eps, packed, w_scale, norm_b);
   const int64_t N = w.size(0);
   TORCH_CHECK(ema::skinny_gemm_supported(p.M, N, p.K), "skinny: unsupported shape");
-  auto y = at::empty({p.M, N}, x.options());
+  TORCH_CHECK(!gelu || (!res && (!norm_w || norm_b)),
+              "skinny: the GeLU epilogue takes no residual and no RMSNorm prologue");
+  TORCH_CHECK(!norm_b || !res, "skinny: no LayerNorm prologue with the residual epilogue");
+  auto y = wide_out(x, out, p.M, N);
   p.N = (int)N;
   p.y = y.data_ptr();
-  p.ldy = N;
-  int epi = 0;
+  p.ldy = y.stride(0);
+  int epi = gelu ? 4 : 0;
   if (res) {
     TORCH_CHECK(res->is_cuda() && res->scalar_type() == x.scalar_type() && res->dim() == 2 &&
                 res->size(0) == p.M && res->size(1) == N && res->stride(1) == 1 &&
@@ -1051,8 +1069,10 @@ static at::Tensor qkv_rope_cache(const at::Tensor& x, const at::Tensor& w,
                                  const c10::optional<at::Tensor>& w_scale,
                                  const c10::optional<at::Tensor>& kv_scale, int wide_fb,
                                  int64_t seqs, const c10::optional<at::Tensor>& kv_len,
-                                 const c10::optional<at::Tensor>& page_table) {
-  auto p = skinny_args(x, w, norm_w, eps, packed, w_scale);
+                                 const c10::optional<at::Tensor>& page_table,
+                                 const c10::optional<at::Tensor>& norm_b = c10::nullopt) {
+  auto p = skinny_args(x, w, norm_w, eps, packed, w_scale, norm_b);
+  TORCH_CHECK(!norm_b || seqs == 0, "skinny qkv: no LayerNorm prologue in the multi-row geometry");
   const int64_t N = w.size(0);
   TORCH_CHECK(N == ng * (r + 2) * hd && hd % 8 == 0, "skinny qkv: w rows != ng * (r + 2) * hd");
   // FP8 KV cache: uint8 (e4m3fn) caches and fp32 scales [2, ng]
@@ -1157,9 +1177,10 @@ at::Tensor skinny_qkv_rope_cache(const at::Tensor& x, const at::Tensor& w,
                                  const c10::optional<at::Tensor>& w_scale,
                                  const c10::optional<at::Tensor>& kv_scale, int64_t seqs,
                                  const c10::optional<at::Tensor>& kv_len,
-                                 const c10::optional<at::Tensor>& page_table) {
+                                 const c10::optional<at::Tensor>& page_table,
+                                 const c10::optional<at::Tensor>& norm_b) {
   return qkv_rope_cache(x, w, norm_w, eps, ng, r, hd, cos, sin, pos, kcache, vcache, slot_t, slot,
-                        packed, w_scale, kv_scale, -1, seqs, kv_len, page_table);
+                        packed, w_scale, kv_scale, -1, seqs, kv_len, page_table, norm_b);
 }
 
 // ---------------------------------------------------------------- wide GEMM (decode, 33-64 rows)
@@ -1190,10 +1211,11 @@ static int wide_fb(int64_t fb) {
 at::Tensor wide_gemm(const at::Tensor& x, const at::Tensor& w,
                      const c10::optional<at::Tensor>& res,
                      const c10::optional<at::Tensor>& w_scale, int64_t fb,
-                     const c10::optional<at::Tensor>& out) {
+                     const c10::optional<at::Tensor>& out, bool gelu) {
   auto p = skinny_args(x, w, c10::nullopt, 0.0, true, w_scale);
   const int64_t N = w.size(0);
   TORCH_CHECK(ema::wide_gemm_supported(p.M, N, p.K), "wide_gemm: unsupported shape");
+  TORCH_CHECK(!gelu || !res, "wide_gemm: the GeLU epilogue takes no residual");
   auto y = wide_out(x, out, p.M, N);
   p.N = (int)N;
   p.y = y.data_ptr();
@@ -1206,7 +1228,7 @@ at::Tensor wide_gemm(const at::Tensor& x, const at::Tensor& w,
     p.res = res->data_ptr();
     p.ldr = res->stride(0);
   }
-  ema::wide_gemm_ex(p, res ? 1 : 0, dtype_code(x), wide_fb(fb), cur_stream());
+  ema::wide_gemm_ex(p, res ? 1 : gelu ? 4 : 0, dtype_code(x), wide_fb(fb), cur_stream());
   return y;
 }
 
@@ -2111,7 +2133,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("w_scale") = py::none());
   m.def("skinny_gemm_supported", &skinny_gemm_supported);
   m.def("skinny_norm_gemm", &skinny_norm_gemm, py::arg("x"), py::arg("w"), py::arg("norm_w"),
-        py::arg("eps"), py::arg("res"), py::arg("packed") = false, py::arg("w_scale") = py::none());
+        py::arg("eps"), py::arg("res"), py::arg("packed") = false, py::arg("w_scale") = py::none(),
+        py::arg("norm_b") = py::none(), py::arg("gelu") = false, py::arg("out") = py::none());
   m.def("skinny_norm_glu", &skinny_norm_glu, py::arg("x"), py::arg("w1"), py::arg("norm_w"),
         py::arg("eps"), py::arg("kind"), py::arg("packed") = false, py::arg("packed_tail") = 0,
         py::arg("w_scale") = py::none());
@@ -2122,11 +2145,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("cos"), py::arg("sin"), py::arg("pos"), py::arg("kcache"), py::arg("vcache"),
         py::arg("slot_t"), py::arg("slot"), py::arg("packed") = false,
         py::arg("w_scale") = py::none(), py::arg("kv_scale") = py::none(), py::arg("seqs") = 0,
-        py::arg("kv_len") = py::none(), py::arg("page_table") = py::none());
+        py::arg("kv_len") = py::none(), py::arg("page_table") = py::none(),
+        py::arg("norm_b") = py::none());
   m.def("wide_gemm_supported", &wide_gemm_supported);
   m.def("wide_gemm_split", &ema::wide_gemm_split, py::arg("nblocks"));
   m.def("wide_gemm", &wide_gemm, py::arg("x"), py::arg("w_packed"), py::arg("res") = py::none(),
-        py::arg("w_scale") = py::none(), py::arg("fb") = 0, py::arg("out") = py::none());
+        py::arg("w_scale") = py::none(), py::arg("fb") = 0, py::arg("out") = py::none(),
+        py::arg("gelu") = false);
   m.def("wide_glu", &wide_glu, py::arg("x"), py::arg("w1_packed"), py::arg("kind"),
         py::arg("w_scale") = py::none(), py::arg("fb") = 0, py::arg("out") = py::none());
   m.def("wide_qkv_rope_cache", &wide_qkv_rope_cache, py::arg("x"), py::arg("w_packed"),

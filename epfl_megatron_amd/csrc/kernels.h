@@ -511,7 +511,7 @@ bool skinny_gemm_supported(int64_t M, int64_t N, int64_t K);
 void skinny_gemm(const void* x, const void* w, void* y, int64_t M, int64_t N, int64_t K, int dt,
                  hipStream_t s);
 // Fused decode forms (skinny_gemm.hip header): epi 0 plain, 1 residual add,
-// 2 GLU (N = F, W [2F, K]), 3 GQA QKV with rotary + KV-cache write.
+// 2 GLU (N = F, W [2F, K]), 3 GQA QKV with rotary + KV-cache write, 4 erf GeLU.
 struct SkinnyArgs {
   const void* x;        // [M, K]
   const void* w;        // [N, K] (GLU: [2N, K])
@@ -519,6 +519,8 @@ struct SkinnyArgs {
   int M, N, K;
   int64_t ldy;
   const void* norm_w;   // RMSNorm weight [K] (nullptr: no norm prologue)
+  const void* norm_b;   // non-null: norm_w / norm_b are a LayerNorm's gamma / beta [K] (M <= 16;
+                        // epi 0, 3, 4)
   float eps;
   const void* res;      // EPI_RES: residual [M, ldr]
   int64_t ldr;

@@ -19,7 +19,9 @@ typedef __attribute__((ext_vector_type(2))) float f2;
 typedef __attribute__((ext_vector_type(4))) int i4;
 typedef __attribute__((ext_vector_type(2))) int i2;
 
-enum { EPI_PLAIN = 0, EPI_RES = 1, EPI_GLU = 2, EPI_QKV = 3 };
+enum { EPI_PLAIN = 0, EPI_RES = 1, EPI_GLU = 2, EPI_QKV = 3, EPI_ACT = 4 };
+// norm prologue of the skinny kernels (SkinnyArgs::norm_w / norm_b)
+enum { NORM_NONE = 0, NORM_RMS = 1, NORM_LN = 2 };
 
 template <typename T>
 __device__ __forceinline__ f4 mfma16x16x32(typename fa::MT<T>::x8 a, typename fa::MT<T>::x8 b, f4 c) {
@@ -368,6 +370,10 @@ __device__ __forceinline__ void epilogue(const SkinnyArgs& p, int blk, const f4&
     }
     *reinterpret_cast<typename fa::MT<T>::x4*>(dst) = o;
     return;
+  }
+  if constexpr (EPI == EPI_ACT) {  // gelu_fwd_k on the rounded product
+#pragma unroll
+    for (int i = 0; i < 4; ++i) o[i] = (T)gelu_erf((float)o[i]);
   }
   *reinterpret_cast<typename fa::MT<T>::x4*>(y + (int64_t)m * p.ldy + n) = o;
 }

@@ -23,7 +23,15 @@
 //   * NORM: RMSNorm of X in the prologue.  Each wave sums the squares of the X
 //     slice it streams anyway, the 8 partials meet in LDS, and every B operand
 //     is formed as T(T(x * rstd) * g) — the rounding of rmsnorm_fwd_k.
+//   * NORM_LN: LayerNorm of X in the prologue (the Falcon block).  Each wave
+//     leaves its slice's sum and its sum of squares about its own slice mean
+//     in LDS; the 8 pairs combine in wave order by Chan's formula (never
+//     E[x^2] - mu^2), and every B operand is T((x - mu) * rstd * g + beta) —
+//     the single rounding of layernorm_fwd_k.  Built for <= 16 rows and the
+//     plain, QKV and activation epilogues.
 //   * EPI_RES: Y = T(T(acc) + R), the residual add of the block.
+//   * EPI_ACT: Y = T(gelu_erf(T(acc))), the non-GLU MLP's activation: bit for
+//     bit gelu_fwd of the plain form (one device function, act_math.h).
 //   * EPI_GLU: the 16 W rows are 8 "up" rows f0.. and the 8 matching "gate"
 //     rows F + f0..; Y[m, f] = T(x1 * act(x2)) over the rounded pair (the
 //     glu_fwd_k numerics); grid = F / 8.
@@ -89,7 +97,8 @@ namespace {
 // one MFMA per row block, so the weight stream is read once for 32 rows).
 // W8: e4m3 weights, a ring slot = one 16-B piece = SPU = 2 k-steps.
 // W4: MXFP4 weights, a ring slot = one 16-B piece + its scale dword = 4 k-steps.
-template <typename T, int WAVES, bool NORM, int EPI, int ACT, bool PACKED, int MB, bool W8 = false,
+// NORM: the prologue's norm kind (NORM_NONE / NORM_RMS / NORM_LN)
+template <typename T, int WAVES, int NORM, int EPI, int ACT, bool PACKED, int MB, bool W8 = false,
           bool W4 = false>
 __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) {
   typedef typename fa::MT<T>::x8 x8;
@@ -110,12 +119,16 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) 
   // W4: whole four-step slots; one row block keeps the W8 forms' 16 steps (4
   // pieces + 4 scale dwords), two un-normed row blocks 12 (K = 11008: 43 =
   // 3 x 12 + 7) beside fewer X fragments than the 14 of the other forms
-  constexpr int U = W4 ? (MB == 1 ? 2 * SKINNY_U : NORM ? SKINNY_U : 12)
-                       : MB == 2 && !NORM ? 14 : W8 && MB == 1 ? 2 * SKINNY_U : SKINNY_U;
+  // LayerNorm: 8 steps in every weight format (beta rides the ring beside gamma)
+  constexpr int U = NORM == NORM_LN ? SKINNY_U
+                    : W4 ? (MB == 1 ? 2 * SKINNY_U : NORM ? SKINNY_U : 12)
+                         : MB == 2 && !NORM ? 14 : W8 && MB == 1 ? 2 * SKINNY_U : SKINNY_U;
+  static_assert(NORM != NORM_LN || MB == 1, "the LayerNorm prologue is built for <= 16 rows");
   constexpr int US = U / SPU;  // ring slots
   static_assert(U % SPU == 0, "ring slots hold whole pieces");
   __shared__ f4 part[WAVES][MB][64];
   __shared__ float ssq[WAVES][16 * MB];
+  __shared__ float ssm[NORM == NORM_LN ? WAVES : 1][16 * MB];  // LayerNorm: the slice sums
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int M = p.M, N = p.N, K = p.K;
   const T* __restrict__ x = (const T*)p.x;
@@ -161,6 +174,7 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) 
     xr[mb] = x + (int64_t)(xon[mb] ? r + 16 * mb : 0) * K + kbeg + kc;
   }
   const T* gr = NORM ? (const T*)p.norm_w + kbeg + kc : nullptr;
+  const T* br = NORM == NORM_LN ? (const T*)p.norm_b + kbeg + kc : nullptr;
   const int nblk = steps / U;  // full ring blocks; the < U leftover steps run after them
 
   // Ring of U k-steps: the W fragment (nontemporal: each weight byte is read
@@ -170,7 +184,7 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) 
   // prologue: the weight stream starts at kernel entry, not after the norm's
   // reduction and barrier.
   wslot a[US];
-  x8 xv[MB][U], gv[U];
+  x8 xv[MB][U], gv[U], bv[U];
   if (nblk > 0) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -178,6 +192,7 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) 
 #pragma unroll
       for (int mb = 0; mb < MB; ++mb) xv[mb][u] = *reinterpret_cast<const x8*>(xr[mb] + 32 * u);
       if constexpr (NORM) gv[u] = *reinterpret_cast<const x8*>(gr + 32 * u);
+      if constexpr (NORM == NORM_LN) bv[u] = *reinterpret_cast<const x8*>(br + 32 * u);
     }
   }
   // W8: wave 0 fetches the block's row scales here, with the stream's first loads
@@ -186,10 +201,59 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) 
     if (wave == 0) pre.sc = epi_scale<EPI>(p, blockIdx.x, -1, lane);
   }
 
-  float rs[MB];  // rstd of X rows r + 16 mb (NORM)
+  float rs[MB], mu[MB];  // rstd (NORM) and mean (LayerNorm) of X rows r + 16 mb
 #pragma unroll
-  for (int mb = 0; mb < MB; ++mb) rs[mb] = 1.f;
-  if constexpr (NORM) {
+  for (int mb = 0; mb < MB; ++mb) rs[mb] = 1.f, mu[mb] = 0.f;
+  if constexpr (NORM == NORM_LN) {
+    // LayerNorm statistics without E[x^2] - mu^2: the wave sums its slice, then
+    // the squares about its own slice mean (the slice read again from L2, 8
+    // loads in flight per round as below); the waves' (sum, centred squares)
+    // meet in LDS once and combine in wave order by Chan's formula for equal
+    // counts: M2 = sum_w (M2_w + kq (mean_w - mu)^2).
+    auto sweep = [&](float centre, auto square_c) {  // sum of (x - centre) or of its square
+      constexpr int mb = 0;
+      float acc = 0.f;
+      for (int s0 = 0; s0 < steps; s0 += 8) {
+        x8 v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const int s = s0 + i < steps ? s0 + i : steps - 1;
+          v[i] = *reinterpret_cast<const x8*>(xr[mb] + 32 * s);
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          const float keep = s0 + i < steps ? 1.f : 0.f;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const float d = (float)v[i][e] - centre;
+            acc += keep * (decltype(square_c)::value ? d * d : d);
+          }
+        }
+      }
+      acc += __shfl_xor(acc, 16, 64);
+      acc += __shfl_xor(acc, 32, 64);
+      return acc;
+    };
+    const float sm = sweep(0.f, std::false_type{});
+    const float sq = sweep(sm / (float)kq, std::true_type{});
+    if (lane < 16) {
+      ssm[wave][lane] = sm;
+      ssq[wave][lane] = sq;
+    }
+    __syncthreads();
+    float tot = 0.f;
+#pragma unroll
+    for (int i = 0; i < WAVES; ++i) tot += ssm[i][r];  // fixed order
+    const float m = tot / (float)K;
+    float m2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < WAVES; ++i) {
+      const float d = ssm[i][r] / (float)kq - m;
+      m2 += ssq[i][r] + (float)kq * d * d;
+    }
+    mu[0] = m;
+    rs[0] = rsqrtf(m2 / (float)K + p.eps);
+  } else if constexpr (NORM) {
     // sum of squares of this wave's X slice: 8 loads issued per round before
     // any is used (a load-then-use loop waits out one L2 round trip per step)
 #pragma unroll
@@ -226,10 +290,15 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) 
     }
   }
   // B operand: X (or its RMSNorm, rounded like rmsnorm_fwd_k) of row block mb
-  auto bop = [&](const x8& v, const x8& g, int mb) {
+  // (LayerNorm: one rounding, the numerics of layernorm_fwd_k)
+  auto bop = [&](const x8& v, const x8& g, const x8& bt, int mb) {
     x8 o;
     if constexpr (!NORM) {
       o = v;
+    } else if constexpr (NORM == NORM_LN) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        o[e] = (T)(((float)v[e] - mu[mb]) * rs[mb] * (float)g[e] + (float)bt[e]);
     } else {
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
@@ -254,7 +323,7 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) 
         const x8 af = afrag(a[u], h);
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb)
-          acc[mb] = mfma16x16x32<T>(af, bop(xv[mb][SPU * u + h], gv[SPU * u + h], mb), acc[mb]);
+          acc[mb] = mfma16x16x32<T>(af, bop(xv[mb][SPU * u + h], gv[SPU * u + h], bv[SPU * u + h], mb), acc[mb]);
       }
       if constexpr (REFILL) {
         const int s = (blk + 1) * U + SPU * u;
@@ -265,6 +334,8 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) 
           for (int mb = 0; mb < MB; ++mb)
             xv[mb][SPU * u + h] = *reinterpret_cast<const x8*>(xr[mb] + 32 * (s + h));
           if constexpr (NORM) gv[SPU * u + h] = *reinterpret_cast<const x8*>(gr + 32 * (s + h));
+          if constexpr (NORM == NORM_LN)
+            bv[SPU * u + h] = *reinterpret_cast<const x8*>(br + 32 * (s + h));
         }
       }
       // keep {MFMA u, refill u} in program order: hipcc would otherwise
@@ -319,6 +390,7 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) 
             for (int mb = 0; mb < MB; ++mb)
               xv[mb][SPU * u + h] = *reinterpret_cast<const x8*>(xr[mb] + 32 * s);
             if constexpr (NORM) gv[SPU * u + h] = *reinterpret_cast<const x8*>(gr + 32 * s);
+            if constexpr (NORM == NORM_LN) bv[SPU * u + h] = *reinterpret_cast<const x8*>(br + 32 * s);
           }
         }
       }
@@ -331,7 +403,7 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) 
           const x8 af = afrag(a[u], h);
 #pragma unroll
           for (int mb = 0; mb < MB; ++mb)
-            acc[mb] = mfma16x16x32<T>(af, bop(xv[mb][SPU * u + h], gv[SPU * u + h], mb), acc[mb]);
+            acc[mb] = mfma16x16x32<T>(af, bop(xv[mb][SPU * u + h], gv[SPU * u + h], bv[SPU * u + h], mb), acc[mb]);
         }
       }
     }
@@ -370,7 +442,10 @@ __global__ __launch_bounds__(64 * WAVES) void skinny_gemm_k(const SkinnyArgs p) 
 // unit's 512 B / 32.
 // MR: EPI_QKV with the multi-row geometry (SkinnyArgs::seqs) compiled in; the
 // forms without it hold no trace of it (qkv_multi, skinny_epi.h).
-template <typename T, bool NORM, int EPI, int ACT, int STEPS, int U, bool PACKED, int MB,
+// NORM_LN: the LayerNorm statistics and the normalisation run once per
+// workgroup on the register-resident X (sum, then the squares about the wave's
+// own slice mean; one LDS meeting as in the RMS form).
+template <typename T, int NORM, int EPI, int ACT, int STEPS, int U, bool PACKED, int MB,
           bool W8 = false, bool W4 = false, bool MR = false>
 __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
   typedef typename fa::MT<T>::x8 x8;
@@ -387,6 +462,9 @@ __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
   __shared__ f4 part[2][WAVES][MB][64];
   __shared__ float ssq[WAVES][16 * MB];
   __shared__ x8 gsh[NORM ? WAVES : 1][64];  // NORM: each wave's gamma slice
+  __shared__ x8 bsh[NORM == NORM_LN ? WAVES : 1][64];    // LayerNorm: and its beta slice
+  __shared__ float ssm[NORM == NORM_LN ? WAVES : 1][16];  // LayerNorm: the slice sums
+  static_assert(NORM != NORM_LN || MB == 1, "the LayerNorm prologue is built for <= 16 rows");
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int M = p.M, N = p.N, K = p.K;
   const T* __restrict__ x = (const T*)p.x;
@@ -517,6 +595,8 @@ __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
   // registers; loading them after the norm reduction cost two more round trips)
   x8 gl{};
   if constexpr (NORM) gl = *reinterpret_cast<const x8*>((const T*)p.norm_w + kbeg + 8 * lane);
+  x8 bl{};
+  if constexpr (NORM == NORM_LN) bl = *reinterpret_cast<const x8*>((const T*)p.norm_b + kbeg + 8 * lane);
   __builtin_amdgcn_sched_barrier(0);
   wslot a[US];
   // Two normed row blocks keep 2 x 16 X fragments and spill ~0.5 KB per lane
@@ -533,7 +613,56 @@ __global__ __launch_bounds__(512) void skinny_pgemm_k(const SkinnyArgs p) {
 #pragma unroll
     for (int u = 0; u < US; ++u) a[u] = sload(wr + ws * u, sr + ss * u);
   }
-  if constexpr (NORM) {
+  if constexpr (NORM == NORM_LN) {
+    constexpr float kq = 32.f * STEPS;  // the wave's slice of a row
+    float sm = 0.f, sq = 0.f;
+#pragma unroll
+    for (int s = 0; s < STEPS; ++s) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) sm += (float)xs[0][s][e];
+    }
+    sm += __shfl_xor(sm, 16, 64);
+    sm += __shfl_xor(sm, 32, 64);
+    const float mw = sm / kq;
+#pragma unroll
+    for (int s = 0; s < STEPS; ++s) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float d = (float)xs[0][s][e] - mw;
+        sq += d * d;
+      }
+    }
+    sq += __shfl_xor(sq, 16, 64);
+    sq += __shfl_xor(sq, 32, 64);
+    if (lane < 16) {
+      ssm[wave][lane] = sm;
+      ssq[wave][lane] = sq;
+    }
+    gsh[wave][lane] = gl;
+    bsh[wave][lane] = bl;
+    __syncthreads();
+    // Chan's formula for equal counts, in wave order: deterministic
+    float tot = 0.f;
+#pragma unroll
+    for (int i = 0; i < WAVES; ++i) tot += ssm[i][r];
+    const float mu = tot / (float)K;
+    float m2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < WAVES; ++i) {
+      const float d = ssm[i][r] / kq - mu;
+      m2 += ssq[i][r] + kq * d * d;
+    }
+    const float rs = rsqrtf(m2 / (float)K + p.eps);
+    // one rounding, as layernorm_fwd_k; step s, lane group q reads chunk 4 s + q
+#pragma unroll
+    for (int s = 0; s < STEPS; ++s) {
+      const x8 g = gsh[wave][4 * s + (lane >> 4)], bt = bsh[wave][4 * s + (lane >> 4)];
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        xs[0][s][e] = (T)(((float)xs[0][s][e] - mu) * rs * (float)g[e] + (float)bt[e]);
+      if (!xon[0]) xs[0][s] = x8{};
+    }
+  } else if constexpr (NORM) {
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
       float ss = 0.f;
@@ -666,9 +795,10 @@ int num_cus() {
 // persistent skinny_pgemm_k on min(blocks, CUs) workgroups.
 // one persistent form on g workgroups (all ten template arguments spelled out);
 // EPI_QKV calls with the multi-row geometry take the form compiled for it
+// (none with the LayerNorm prologue, which the host refuses for that geometry)
 #define EMA_PG(g, ...)                                                                        \
   do {                                                                                        \
-    if constexpr (EPI == EPI_QKV) {                                                           \
+    if constexpr (EPI == EPI_QKV && NORM != NORM_LN) {                                        \
       if (p.seqs) {                                                                           \
         hipLaunchKernelGGL((skinny_pgemm_k<__VA_ARGS__, true>), dim3((unsigned)(g)), dim3(512), \
                            0, s, p);                                                          \
@@ -679,18 +809,24 @@ int num_cus() {
                        s, p);                                                                 \
   } while (0)
 
-template <typename T, int WAVES, int STEPS, bool NORM, int EPI, int ACT>
+// MB2: the two-row-block forms (17-32 rows) exist; the LayerNorm prologue is
+// built for one row block only (the host refuses more rows)
+template <typename T, int WAVES, int STEPS, int NORM, int EPI, int ACT>
 void launch(const SkinnyArgs& p, hipStream_t s) {
   const int nblocks = EPI == EPI_GLU ? p.N / 8 : p.N / 16;
+  constexpr bool MB2 = NORM != NORM_LN;
   if constexpr (WAVES == 8) {
     if (p.w_mx) {  // MXFP4 weights: packed 8-wave forms only (checked by the host)
       if constexpr (STEPS == 0) {
-        if (p.M > 16)
-          hipLaunchKernelGGL((skinny_gemm_k<T, 8, NORM, EPI, ACT, true, 2, false, true>),
-                             dim3((unsigned)nblocks), dim3(512), 0, s, p);
-        else
-          hipLaunchKernelGGL((skinny_gemm_k<T, 8, NORM, EPI, ACT, true, 1, false, true>),
-                             dim3((unsigned)nblocks), dim3(512), 0, s, p);
+        if constexpr (MB2) {
+          if (p.M > 16) {
+            hipLaunchKernelGGL((skinny_gemm_k<T, 8, NORM, EPI, ACT, true, 2, false, true>),
+                               dim3((unsigned)nblocks), dim3(512), 0, s, p);
+            return;
+          }
+        }
+        hipLaunchKernelGGL((skinny_gemm_k<T, 8, NORM, EPI, ACT, true, 1, false, true>),
+                           dim3((unsigned)nblocks), dim3(512), 0, s, p);
       } else {
         // the ring holds one whole unit: 4 / 8 pieces (+ scale dwords) per wave at
         // K = 4096 / 8192, at most the register ring of the W8 forms (two normed
@@ -698,45 +834,56 @@ void launch(const SkinnyArgs& p, hipStream_t s) {
         // which they spill less than their W8 twins; the decode layer does not
         // call them)
         const int g = nblocks < num_cus() ? nblocks : num_cus();
-        if (STEPS == 16 && p.M > 16)
-          EMA_PG(g, T, NORM, EPI, ACT, STEPS, NORM ? 8 : STEPS, true, STEPS == 16 ? 2 : 1, false, true);
-        else
-          EMA_PG(g, T, NORM, EPI, ACT, STEPS, STEPS, true, 1, false, true);
+        if constexpr (MB2) {
+          if (STEPS == 16 && p.M > 16) {
+            EMA_PG(g, T, NORM, EPI, ACT, STEPS, NORM ? 8 : STEPS, true, STEPS == 16 ? 2 : 1, false, true);
+            return;
+          }
+        }
+        EMA_PG(g, T, NORM, EPI, ACT, STEPS, STEPS, true, 1, false, true);
       }
       return;
     }
     if (p.w_scale) {  // e4m3 weights: packed 8-wave forms only (checked by the host)
       if constexpr (STEPS == 0) {
-        if (p.M > 16)
-          hipLaunchKernelGGL((skinny_gemm_k<T, 8, NORM, EPI, ACT, true, 2, true>), dim3((unsigned)nblocks),
-                             dim3(512), 0, s, p);
-        else
-          hipLaunchKernelGGL((skinny_gemm_k<T, 8, NORM, EPI, ACT, true, 1, true>), dim3((unsigned)nblocks),
-                             dim3(512), 0, s, p);
+        if constexpr (MB2) {
+          if (p.M > 16) {
+            hipLaunchKernelGGL((skinny_gemm_k<T, 8, NORM, EPI, ACT, true, 2, true>),
+                               dim3((unsigned)nblocks), dim3(512), 0, s, p);
+            return;
+          }
+        }
+        hipLaunchKernelGGL((skinny_gemm_k<T, 8, NORM, EPI, ACT, true, 1, true>), dim3((unsigned)nblocks),
+                           dim3(512), 0, s, p);
       } else {
         // 16 k-steps in flight = 8 pieces per wave: the register ring of the
         // 8-deep 16-bit forms, the whole block of a K = 4096 stream
         const int g = nblocks < num_cus() ? nblocks : num_cus();
-        if (STEPS == 16 && p.M > 16)
-          EMA_PG(g, T, NORM, EPI, ACT, STEPS, 16, true, STEPS == 16 ? 2 : 1, true, false);
-        else
-          EMA_PG(g, T, NORM, EPI, ACT, STEPS, 16, true, 1, true, false);
+        if constexpr (MB2) {
+          if (STEPS == 16 && p.M > 16) {
+            EMA_PG(g, T, NORM, EPI, ACT, STEPS, 16, true, STEPS == 16 ? 2 : 1, true, false);
+            return;
+          }
+        }
+        EMA_PG(g, T, NORM, EPI, ACT, STEPS, 16, true, 1, true, false);
       }
       return;
     }
   }
   if constexpr (STEPS == 0) {
-    if (p.M > 16) {  // 17-32 rows: two row blocks per W fragment
-      if constexpr (WAVES == 8) {
-        if (p.packed) {
-          hipLaunchKernelGGL((skinny_gemm_k<T, WAVES, NORM, EPI, ACT, true, 2>),
-                             dim3((unsigned)nblocks), dim3(64 * WAVES), 0, s, p);
-          return;
+    if constexpr (MB2) {
+      if (p.M > 16) {  // 17-32 rows: two row blocks per W fragment
+        if constexpr (WAVES == 8) {
+          if (p.packed) {
+            hipLaunchKernelGGL((skinny_gemm_k<T, WAVES, NORM, EPI, ACT, true, 2>),
+                               dim3((unsigned)nblocks), dim3(64 * WAVES), 0, s, p);
+            return;
+          }
         }
+        hipLaunchKernelGGL((skinny_gemm_k<T, WAVES, NORM, EPI, ACT, false, 2>),
+                           dim3((unsigned)nblocks), dim3(64 * WAVES), 0, s, p);
+        return;
       }
-      hipLaunchKernelGGL((skinny_gemm_k<T, WAVES, NORM, EPI, ACT, false, 2>), dim3((unsigned)nblocks),
-                         dim3(64 * WAVES), 0, s, p);
-      return;
     }
     if constexpr (WAVES == 8) {
       if (p.packed) {
@@ -753,7 +900,7 @@ void launch(const SkinnyArgs& p, hipStream_t s) {
     // register-resident X fragments of K = 8192 (16 spilled 92-204 B per lane)
     constexpr int U = STEPS == 32 ? 8 : 16;
     const int g = nblocks < num_cus() ? nblocks : num_cus();
-    if constexpr (STEPS == 16) {
+    if constexpr (STEPS == 16 && MB2) {
       // 17-32 rows: two row blocks, the ring 8 deep beside 2 x 16 X fragments
       // (16 deep for the un-normed forms measured within noise: o_proj 13.6 /
       // 14.5 vs 13.0 / 14.3 us at 24 / 32 rows, profiles/r4as_pskinny_u16.txt)
@@ -780,7 +927,28 @@ void dispatch(const SkinnyArgs& p, int epi, hipStream_t s) {
   // normed 8192-wide forms keep the one-block-per-workgroup kernel
   constexpr int SN = STEPS == 32 ? 0 : STEPS;
 #define EMA_SK(NORM_, EPI_, ACT_) launch<T, WAVES, (NORM_ ? SN : STEPS), NORM_, EPI_, ACT_>(p, s)
+  // LayerNorm prologue (p.norm_b; the Falcon decode layer): built for the
+  // plain, QKV and activation epilogues, <= 16 rows; the 8192-wide forms keep
+  // the one-block-per-workgroup kernel like the RMS ones (the host checks the
+  // combination: csrc/bindings.cpp)
+  // fp16: the persistent LayerNorm forms spill (8-232 B per lane, hipcc keeps
+  // the converted fp32 X between the two passes; profiles/r24a_falcon_isa.txt),
+  // so fp16 takes the one-block-per-workgroup kernel at K = 4096 as well
+  if (p.norm_b) {
+    constexpr int SL = __is_same(T, fp16) ? 0 : SN;
+#define EMA_SKL(EPI_) launch<T, WAVES, SL, NORM_LN, EPI_, 0>(p, s)
+    switch (epi) {
+      case EPI_QKV: EMA_SKL(EPI_QKV); break;
+      case EPI_ACT: EMA_SKL(EPI_ACT); break;
+      default: EMA_SKL(EPI_PLAIN);
+    }
+#undef EMA_SKL
+    return;
+  }
   switch (epi) {
+    case EPI_ACT:  // Y = T(gelu_erf(T(acc))); un-normed (or LayerNorm, above)
+      EMA_SK(false, EPI_ACT, 0);
+      break;
     case EPI_RES:
       nm ? EMA_SK(true, EPI_RES, 0) : EMA_SK(false, EPI_RES, 0);
       break;

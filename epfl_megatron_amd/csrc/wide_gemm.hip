@@ -49,7 +49,7 @@
 // Reduction and epilogue.  With KS > 1 the slices' partial tiles meet in LDS
 // (the dead X ring) and the slice-0 wave adds them in slice order:
 // deterministic.  That wave runs skinny_epi.h's epilogue per row block:
-// plain, residual, the four GLU kinds, QKV with RoPE and the KV-cache write
+// plain, residual, erf GeLU, the four GLU kinds, QKV with RoPE and the KV-cache write
 // (16-bit or e4m3 cache, host / device / per-row slot); e4m3 row scales are
 // applied before the first rounding; its operands are fetched before the
 // k-loop.  No RMSNorm prologue: at these row counts the norm is its own kernel.
@@ -294,6 +294,7 @@ void dispatch(const SkinnyArgs& p, int epi, int fbl, hipStream_t s) {
   switch (epi) {
     case EPI_RES: launch<T, EPI_RES, 0>(p, fbl, s); break;
     case EPI_QKV: launch<T, EPI_QKV, 0>(p, fbl, s); break;
+    case EPI_ACT: launch<T, EPI_ACT, 0>(p, fbl, s); break;
     case EPI_GLU:
       switch (p.act) {
         case 0: launch<T, EPI_GLU, 0>(p, fbl, s); break;

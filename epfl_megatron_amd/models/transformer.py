@@ -31,7 +31,7 @@ from ..parallel.buffers import divide, make_viewless_tensor
 from ..parallel import tensor as tp
 from ..ops.dropout import bias_dropout_add
 from ..utils.trace import trace_range, tracing
-from ..ops.norms import RMSNorm, MixedFusedLayerNorm, _param_sync, rms_norm
+from ..ops.norms import RMSNorm, MixedFusedLayerNorm, _param_sync, rms_norm, layer_norm
 from ..ops.rope import rope_table, apply_rope_ref, rope_qkv_inplace, rope_qkv
 from ..ops._ext import use_native, ext
 from ..parallel.context import chunk_position_ids, ring_attention
@@ -55,6 +55,19 @@ from .utils import attention_mask_func, erf_gelu
 # verify step) takes the same five launches on its sq * b rows under
 # ip.device_multi = "fused" (inference/kv_cache.py); otherwise it runs unfused.
 _DECODE_FUSED = os.environ.get("EMA_DECODE_FUSED", "1") != "0"
+# The Falcon block (parallel attention / MLP off LayerNorms of the same input,
+# erf GeLU, no biases) takes four launches under the same switch:
+# [LayerNorm + QKV + RoPE + KV-cache write] -> decode attention ->
+# [LayerNorm + fc1 + GeLU] -> [(o | y) (Wo | W2)^T + x], and one all-reduce.
+# Fused Falcon decode layers run so far (tests assert which path ran):
+decode_parallel_calls = {"fused": 0}
+# H = 8192 (Falcon-40B): the in-kernel LayerNorm form is the one-block-per-
+# workgroup kernel, which recomputes the statistics in each of its N / 16
+# workgroups.  The layernorm kernel followed by the un-normed persistent form
+# is 1.4-2.3x faster on both LayerNorm-fed products (fc1 + GeLU 102-107 us
+# against 164-246 us at 1-16 rows; profiles/r24b_falcon_decode.txt), so that is
+# the route; EMA_DECODE_LN_SEP_8192=0 takes the in-kernel form (A/B).
+_LN_SEP_8192 = os.environ.get("EMA_DECODE_LN_SEP_8192", "1") != "0"
 # 33-64 rows can run the same fused step through csrc/wide_gemm.hip (X staged
 # in LDS).  EMA_WIDE_GEMM: "auto" (default) takes it under the quantised-weight
 # flags only, whose packed copies nothing else reads at these row counts; with
@@ -666,6 +679,121 @@ class ParallelTransformerLayer(MegatronModule):
         h3 = tp.reduce_from_tensor_model_parallel_region(h3)
         return h3.view(nt, nseq, H)
 
+    def _decode_fused_parallel_ok(self, hidden_states, ip):
+        """One decode step (one row per sequence) of the Falcon block: parallel
+        attention and MLP off LayerNorms of the same input, erf GeLU, no biases,
+        rotary.  Hidden sizes the kernels do not take (Falcon-7B's 4544 is no
+        multiple of 128) keep the generic path."""
+        if not (_DECODE_FUSED and ip is not None and not torch.is_grad_enabled()
+                and hidden_states.is_cuda and hidden_states.dim() == 3
+                and hidden_states.shape[0] == 1
+                and hidden_states.shape[1] <= (64 if _wide_on() else 32)
+                and hidden_states.dtype in (torch.bfloat16, torch.float16)
+                and self.parallel_attn and not self.use_post_ln
+                and not self.apply_residual_connection_post_layernorm
+                and not self.fp32_residual_connection and self.layer_type == LayerType.encoder
+                and (self.hidden_dropout == 0.0 or not self.training)
+                and self.drop_path is None):
+            return False
+        sa, mlp = self.self_attention, self.mlp
+        lns = [self.input_layernorm] + ([self.mlp_layernorm] if self.parallel_layernorm else [])
+        if not (all(isinstance(ln, MixedFusedLayerNorm) for ln in lns)
+                and sa.attention_type == AttnType.self_attn
+                and sa.position_embedding_type == PositionEmbeddingType.rotary
+                and sa.query_key_value.bias is None and sa.dense.bias is None
+                and not mlp.glu_activation and not mlp.use_bias
+                and not mlp.bias_gelu_fusion and not mlp.onnx_safe
+                and not sa.dense.sequence_parallel_enabled
+                and not mlp.dense_4h_to_h.sequence_parallel_enabled
+                and sa.hidden_size_per_attention_head in (64, 128)):
+            return False
+        C = ext()
+        b, H = hidden_states.shape[1:]
+        wq, wo = sa.query_key_value.weight, sa.dense.weight
+        w1, w2 = mlp.dense_h_to_4h.weight, mlp.dense_4h_to_h.weight
+        ws = [wq, wo, w1, w2] + [t for ln in lns for t in (ln.weight, ln.bias)]
+        if any(w.dtype != hidden_states.dtype or not w.is_contiguous() for w in ws):
+            return False
+        # the output product runs over [o | y]: its weight exists as the packed
+        # [Wo | W2] only, both widths whole 256-wide k-step groups
+        if not (decode_pack.ENABLED and decode_pack.cat_packable(wo, w2)):
+            return False
+        ok = C.wide_gemm_supported if b > 32 else C.skinny_gemm_supported
+        if b > 32 and not all(decode_pack.packable(w) for w in (wq, w1)):
+            return False
+        return (ok(b, wq.shape[0], H) and ok(b, w1.shape[0], H)
+                and ok(b, H, wo.shape[1] + w2.shape[1]))
+
+    def _forward_decode_fused_parallel(self, hidden_states, ip, position_ids):
+        """The Falcon decode layer in four launches (csrc/skinny_gemm.hip):
+        [LayerNorm + QKV + RoPE + KV-cache write] -> decode attention ->
+        [LayerNorm + fc1 + GeLU] -> [(o | y) (Wo | W2)^T + x], then ONE
+        all-reduce: nothing reads x + attn on the way to the MLP, so the two
+        row-parallel products are one product over the concatenated K."""
+        decode_parallel_calls["fused"] += 1
+        sa, mlp = self.self_attention, self.mlp
+        ln_a = self.input_layernorm
+        ln_m = self.mlp_layernorm if self.parallel_layernorm else ln_a
+        C = ext()
+        _, b, H = hidden_states.shape
+        x = hidden_states.reshape(b, H)
+        if not x.is_contiguous():
+            x = x.contiguous()
+        ng, r, hd = sa.num_groups_per_partition, sa.q_per_group, sa.hidden_size_per_attention_head
+        kv = LayerKV(ip, sa.layer_number, ng, hd, sa.params_dtype, x.device, 1, b, fused=True)
+        cos, sin = sa._rope(x.device)
+        if position_ids is None:
+            pos = torch.full((b, 1), ip.sequence_len_offset, dtype=torch.long, device=x.device)
+        else:
+            pos = position_ids[:, -1:].long()
+        wq, wo = sa.query_key_value.weight, sa.dense.weight
+        w1, w2 = mlp.dense_h_to_4h.weight, mlp.dense_4h_to_h.weight
+        Ko, F = wo.shape[1], w2.shape[1]
+        # the in-kernel LayerNorm is built for one row block; beyond it (and at
+        # H = 8192 where _LN_SEP_8192 says so) the layernorm kernel runs first and
+        # the projections take the un-normed forms
+        wide = b > 32
+        sep = b > 16 or (H == 8192 and _LN_SEP_8192)
+
+        def stream(w, cat=None):
+            """as in _forward_decode_fused; ``cat``: the pack of [w | cat]"""
+            if _MXFP4_WEIGHTS:
+                pair = mxfp4_weights.packed_mxfp4(w, cat=cat)
+            else:
+                pair = fp8_weights.packed_fp8(w, cat=cat) if _FP8_WEIGHTS else None
+            return pair if pair is not None else (decode_pack.packed(w, cat=cat), None)
+        (pq, sq), (p1, s1), (po, so) = stream(wq), stream(w1), stream(wo, w2)
+        xa = xm = x
+        if sep:
+            xa = layer_norm(x, ln_a.weight, ln_a.bias, ln_a.eps)
+            xm = xa if ln_m is ln_a else layer_norm(x, ln_m.weight, ln_m.bias, ln_m.eps)
+        # o and y meet in one [b, Ko + F] operand: fc1's epilogue writes its
+        # columns directly; the attention output is copied into its own
+        oy = torch.empty(b, Ko + F, dtype=x.dtype, device=x.device)
+        if wide:
+            q = C.wide_qkv_rope_cache(xa, pq, ng, r, hd, cos, sin, pos, kv.kc, kv.vc,
+                                      kv.slot_t, kv.slot, sq, kv.scales)
+        else:
+            q = C.skinny_qkv_rope_cache(xa, wq if pq is None else pq,
+                                        None if sep else ln_a.weight, ln_a.eps, ng, r, hd,
+                                        cos, sin, pos, kv.kc, kv.vc, kv.slot_t, kv.slot,
+                                        pq is not None, sq, kv.scales,
+                                        norm_b=None if sep else ln_a.bias)
+        oy[:, :Ko].copy_(kv.decode(q.view(b, 1, ng * r, hd), sa._window).reshape(b, Ko))
+        # TP rank 0 alone adds the residual, so one all-reduce of [b, H] yields
+        # the partial sums + x (as in _forward_decode_fused)
+        res = x if state.get_tensor_model_parallel_rank() == 0 else None
+        if wide:
+            C.wide_gemm(xm, p1, None, s1, 0, oy[:, Ko:], True)
+            out = C.wide_gemm(oy, po, res, so)
+        else:
+            C.skinny_norm_gemm(xm, w1 if p1 is None else p1, None if sep else ln_m.weight,
+                               ln_m.eps, None, p1 is not None, s1,
+                               norm_b=None if sep else ln_m.bias, gelu=True, out=oy[:, Ko:])
+            out = C.skinny_norm_gemm(oy, po, None, 0.0, res, True, so)
+        out = tp.reduce_from_tensor_model_parallel_region(out)
+        return out.view(1, b, H)
+
     def _forward_fused_residual(self, hidden_states, attention_mask, inference_params,
                                 position_ids):
         ln_out, residual = self.input_layernorm.forward_residual(hidden_states)
@@ -693,6 +821,9 @@ class ParallelTransformerLayer(MegatronModule):
                  inference_params=None, position_ids=None):
         if self._decode_fused_ok(hidden_states, inference_params, position_ids):
             return self._forward_decode_fused(hidden_states, inference_params, position_ids)
+        if self._decode_fused_parallel_ok(hidden_states, inference_params):
+            return self._forward_decode_fused_parallel(hidden_states, inference_params,
+                                                       position_ids)
         if self._fused_residual_ok():
             return self._forward_fused_residual(hidden_states, attention_mask, inference_params,
                                                 position_ids)

@@ -100,23 +100,44 @@ def unpack(p, glu=False, half_tail=0):
     return blocks.reshape(n, k)
 
 
-def packed(w, glu=False, half_tail=0):
-    """Cached packed copy of parameter ``w``, or None when the row-major
-    weight must be streamed (disabled / unsupported shape)."""
-    if not ENABLED or not packable(w):
+def cat_packable(w, cat):
+    """``[w | cat]`` along K packs with both parts on whole k-steps of every
+    wave-independent unit (256: also whole MXFP4 blocks)."""
+    return (packable(w) and packable(cat) and w.shape[0] == cat.shape[0]
+            and w.dtype == cat.dtype and w.device == cat.device)
+
+
+def cached(w, attr, form, cat, build):
+    """``build(tensor)`` of parameter ``w``, or with ``cat`` of ``[w | cat]``
+    along K (the Falcon decode layer's one output product over ``[o | y]``),
+    cached next to ``w`` in the dict ``attr`` under ``form``, or None where the
+    shape does not pack.  The key holds the identity of ``w`` and of ``cat``,
+    so a concatenated copy is rebuilt when either parameter changes."""
+    if not ENABLED or not (packable(w) if cat is None else cat_packable(w, cat)):
         return None
-    form = (bool(glu), int(half_tail))
-    key = (w.data_ptr(), w._version, _WEIGHT_GEN[0], w.dtype, tuple(w.shape))
-    cache = getattr(w, "_ema_decode_packed", None)
+
+    def ident(t):
+        return (t.data_ptr(), t._version, _WEIGHT_GEN[0], t.dtype, tuple(t.shape))
+    form = form + (cat is not None,)
+    key = (ident(w), None if cat is None else ident(cat))
+    cache = getattr(w, attr, None)
     if not isinstance(cache, dict):
         cache = {}
-        w._ema_decode_packed = cache
+        setattr(w, attr, cache)
     hit = cache.get(form)
     if hit is not None and hit[0] == key:
         return hit[1]
-    for f in [f for f, v in cache.items() if v[0] != key]:
-        del cache[f]  # stale forms of an older generation
+    for f in [f for f, v in cache.items() if v[0][0] != key[0]]:
+        del cache[f]  # stale forms of an older generation of w
     with torch.no_grad():
-        p = pack(w.detach(), glu, half_tail)
+        p = build(w.detach() if cat is None else torch.cat((w.detach(), cat.detach()), 1))
     cache[form] = (key, p)
     return p
+
+
+def packed(w, glu=False, half_tail=0, cat=None):
+    """Cached packed copy of parameter ``w`` (``cat``: of ``[w | cat]`` along
+    K), or None when the row-major weight must be streamed (disabled /
+    unsupported shape)."""
+    return cached(w, "_ema_decode_packed", (bool(glu), int(half_tail)), cat,
+                  lambda t: pack(t, glu, half_tail))

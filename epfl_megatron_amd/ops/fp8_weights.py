@@ -138,26 +138,15 @@ def unpack_fp8(p, glu=False, half_tail=0):
     return out.contiguous().view(FP8)
 
 
-def packed_fp8(w, glu=False, half_tail=0):
-    """Cached ``(packed e4m3 weight, fp32 row scales)`` of parameter ``w``, or
+def packed_fp8(w, glu=False, half_tail=0, cat=None):
+    """Cached ``(packed e4m3 weight, fp32 row scales)`` of parameter ``w``
+    (``cat``: of ``[w | cat]`` along K, one scale per concatenated row), or
     None where the 16-bit weights must be streamed (packing disabled /
     unsupported shape)."""
-    if not decode_pack.ENABLED or not decode_pack.packable(w):
-        return None
     pow2 = bool(POW2_SCALES)
-    form = (bool(glu), int(half_tail), pow2)
-    key = (w.data_ptr(), w._version, decode_pack.weight_generation(), w.dtype, tuple(w.shape))
-    cache = getattr(w, "_ema_decode_packed_fp8", None)
-    if not isinstance(cache, dict):
-        cache = {}
-        w._ema_decode_packed_fp8 = cache
-    hit = cache.get(form)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    for f in [f for f, v in cache.items() if v[0] != key]:
-        del cache[f]  # stale forms of an older generation
-    with torch.no_grad():
-        q, scale = quantize_rows(w.detach(), pow2)
-        pair = (pack_fp8(q, glu, half_tail), scale.contiguous())
-    cache[form] = (key, pair)
-    return pair
+
+    def build(t):
+        q, scale = quantize_rows(t, pow2)
+        return pack_fp8(q, glu, half_tail), scale.contiguous()
+    return decode_pack.cached(w, "_ema_decode_packed_fp8", (bool(glu), int(half_tail), pow2),
+                              cat, build)

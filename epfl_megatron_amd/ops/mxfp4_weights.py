@@ -193,24 +193,10 @@ def unpack_mxfp4(wq, ws, glu=False, half_tail=0):
     return codes, _unblocks(torch.cat(eb), n, k // BLOCK, glu)
 
 
-def packed_mxfp4(w, glu=False, half_tail=0):
-    """Cached ``(packed nibbles, e8m0 scale stream)`` of parameter ``w``, or
-    None where the 16-bit weights must be streamed (packing disabled /
-    unsupported shape)."""
-    if not decode_pack.ENABLED or not decode_pack.packable(w):
-        return None
-    form = (bool(glu), int(half_tail))
-    key = (w.data_ptr(), w._version, decode_pack.weight_generation(), w.dtype, tuple(w.shape))
-    cache = getattr(w, "_ema_decode_packed_mxfp4", None)
-    if not isinstance(cache, dict):
-        cache = {}
-        w._ema_decode_packed_mxfp4 = cache
-    hit = cache.get(form)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    for f in [f for f, v in cache.items() if v[0] != key]:
-        del cache[f]  # stale forms of an older generation
-    with torch.no_grad():
-        pair = pack_mxfp4(*quantize_blocks(w.detach()), glu, half_tail)
-    cache[form] = (key, pair)
-    return pair
+def packed_mxfp4(w, glu=False, half_tail=0, cat=None):
+    """Cached ``(packed nibbles, e8m0 scale stream)`` of parameter ``w``
+    (``cat``: of ``[w | cat]`` along K; both widths are multiples of 256, so no
+    block of 32 straddles the seam), or None where the 16-bit weights must be
+    streamed (packing disabled / unsupported shape)."""
+    return decode_pack.cached(w, "_ema_decode_packed_mxfp4", (bool(glu), int(half_tail)), cat,
+                              lambda t: pack_mxfp4(*quantize_blocks(t), glu, half_tail))

@@ -51,7 +51,13 @@ GraphedSamplingDecoder, both started from the same generator state.
 fused=True (the verify step through the fused decode layer) and the lockstep
 decoder on batch * S sequences, the floor a verify step of as many rows can approach.
 
+--arch falcon40b: the same runs on the Falcon-40B block (parallel attention, two
+LayerNorms, erf GeLU; pass a few --layers).  --graph --fused_ab: the captured
+greedy step with the fused decode layer and with EMA_DECODE_FUSED=0's path,
+alternating in one process; reports ms per replay of each.
+
 Usage: python scripts/serve_bench.py [--batches 1,8,32] [--graph [--speculative S [--ngram G]]]
+       [--arch falcon40b --layers 4] [--graph --fused_ab [--reps 3]]
        [--top_k K | --top_p P] [--temperature T]
        [--continuous [--requests N] [--prompt_range LO,HI] [--gen_range LO,HI]
         [--poll_every 1,4,16] [--kv_pages N] [--capacity C]] [--ragged_cost [--reps 3]]
@@ -131,6 +137,12 @@ def main():
     ap.add_argument("--torch_front", action="store_true",
                     help="--speculative: also time the decoder captured with the multi-row step's RoPE "
                          "and cache write in torch (kv_cache.WRITE_MULTI_NATIVE off), alternating")
+    ap.add_argument("--arch", choices=["llama7b", "falcon40b"], default="llama7b",
+                    help="falcon40b: the Falcon-40B block (H 8192, 128 heads / 8 KV groups, head dim "
+                         "64, FFN 32768, parallel attention, two LayerNorms, erf GeLU)")
+    ap.add_argument("--fused_ab", action="store_true",
+                    help="--graph: the captured greedy step with the fused decode layer and with "
+                         "EMA_DECODE_FUSED=0's path, alternating, --reps repetitions each")
     a = ap.parse_args()
     sampling = a.top_k > 0 or a.top_p > 0.0 or a.temperature != 1.0
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=os.environ.get("MASTER_PORT", "29561"),
@@ -154,14 +166,23 @@ def main():
             return sample(logits[:, -1].float(), vocab_size=32000, **skw).view(-1, 1)
         return sample_fused(logits[:, -1], vocab_size=32000, **skw).view(-1, 1)
 
-    argv = ["--num_layers", str(a.layers), "--hidden_size", "4096", "--num_attention_heads", "32",
-            "--ffn_hidden_size", "11008", "--seq_length", "4096", "--max_position_embeddings",
-            "4096", "--position_embedding_type", "rotary", "--use_rms_norm", "--glu_activation",
-            "swiglu", "--no_tie_embed_logits", "--model_name", "llama2", "--use_flash_attn",
-            "--hidden_dropout", "0.0", "--attention_dropout", "0.0", "--bf16",
-            "--tokenizer_type", "NullTokenizer", "--synthetic_vocab_size", "32000",
-            "--make_vocab_size_divisible_by", "128", "--micro_batch_size", "1",
-            "--global_batch_size", "1", "--train_iters", "1", "--lr", "1e-4"]
+    if a.arch == "falcon40b":
+        arch = ["--hidden_size", "8192", "--num_attention_heads", "128",
+                "--num_attention_heads_kv", "8", "--ffn_hidden_size", "32768",
+                "--seq_length", "2048", "--max_position_embeddings", "2048", "--parallel_attn",
+                "--parallel_layernorm", "--no_bias_gelu_fusion", "--no_bias_dropout_fusion",
+                "--model_name", "falcon"]
+    else:
+        arch = ["--hidden_size", "4096", "--num_attention_heads", "32", "--ffn_hidden_size",
+                "11008", "--seq_length", "4096", "--max_position_embeddings", "4096",
+                "--use_rms_norm", "--glu_activation", "swiglu", "--no_tie_embed_logits",
+                "--model_name", "llama2"]
+    argv = ["--num_layers", str(a.layers)] + arch + [
+        "--position_embedding_type", "rotary", "--use_flash_attn",
+        "--hidden_dropout", "0.0", "--attention_dropout", "0.0", "--bf16",
+        "--tokenizer_type", "NullTokenizer", "--synthetic_vocab_size", "32000",
+        "--make_vocab_size_divisible_by", "128", "--micro_batch_size", "1",
+        "--global_batch_size", "1", "--train_iters", "1", "--lr", "1e-4"]
     if a.fp8_weights:
         argv.append("--inference_fp8_weights")
     if a.mxfp4_weights:
@@ -181,6 +202,8 @@ def main():
         return ragged_cost(a, m)
     if a.graph and a.speculative:
         return speculative(a, m, sampling, skw)
+    if a.graph and a.fused_ab:
+        return fused_ab(a, m)
     res = []
     for B in [int(x) for x in a.batches.split(",")]:
         total = a.prompt + a.gen
@@ -222,6 +245,45 @@ def main():
              "prompt": a.prompt, "gen": a.gen, "prefill_ms": round(1e3 * (t1 - t0), 2),
              "decode_ms_per_step": round(1e3 * (t2 - t1) / steps, 3),
              "decode_tokens_per_s": round(B * steps / (t2 - t1), 1)}
+        print(json.dumps(r), flush=True)
+        res.append(r)
+    return res
+
+
+def fused_ab(a, m):
+    """--graph --fused_ab: ms per replay of GraphedGreedyDecoder captured with
+    the fused decode layer and with the unfused path, from the same prompt,
+    alternating in one process."""
+    import torch
+    from epfl_megatron_amd.models import transformer
+    from epfl_megatron_amd.inference.forward_step import InferenceParams
+    from epfl_megatron_amd.inference.hip_graph import GraphedGreedyDecoder
+    res = []
+    for B in [int(x) for x in a.batches.split(",")]:
+        total = a.prompt + a.gen
+        torch.manual_seed(0)
+        prompt = torch.randint(0, 32000, (B, a.prompt), device="cuda")
+        pos = torch.arange(total, device="cuda")[None].expand(B, -1)
+        decs, first = {}, None
+        with torch.no_grad():
+            for fused in (True, False):
+                transformer._DECODE_FUSED = fused
+                ip = InferenceParams(B, total)
+                first = m(prompt, pos[:, :a.prompt], None, inference_params=ip)[:, -1] \
+                    .argmax(-1, keepdim=True)
+                ip.sequence_len_offset += a.prompt
+                decs[fused] = GraphedGreedyDecoder(m, ip, B, a.gen)
+                decs[fused].start(first, a.prompt)  # warm-up forward and capture
+            transformer._DECODE_FUSED = True
+            ms = {True: [], False: []}
+            for _ in range(a.reps):
+                for fused in (True, False):
+                    decs[fused].start(first, a.prompt)
+                    _, dt = _timed(lambda: [decs[fused].step() for _ in range(a.gen - 1)])
+                    ms[fused].append(round(1e3 * dt / (a.gen - 1), 4))
+        r = {"mode": "fused_ab", "arch": a.arch, "layers": a.layers, "batch": B,
+             "mxfp4_weights": bool(a.mxfp4_weights), "fp8_weights": bool(a.fp8_weights),
+             "fused_ms_per_replay": ms[True], "unfused_ms_per_replay": ms[False]}
         print(json.dumps(r), flush=True)
         res.append(r)
     return res
