@@ -1572,12 +1572,19 @@ void sample_tail(const at::Tensor& logits, at::Tensor tokens, at::Tensor history
 // Ragged tails (inference/continuous.py): per-row state hist_idx / slot / pos /
 // limit int64 [b], kv_len / active int32 [b], tick int64 [1]; ctl / fctl as in
 // sample_tail (the greedy form, sample == false, reads only ctl[4] = stop_id);
-// ctl[5] receives the number of rows still active.
+// ctl[5] receives the number of rows still active.  Optional, the per-row form
+// (RaggedRows in kernels.h): row_ctl int64 [b, 4] = [seed, offset0, top_k,
+// stop_id] with row_fctl float32 [b, 2] = [temperature, top_p] (both or neither,
+// sample only); logprob float32 [b] / hist_logprob float32 [b, H] receive the
+// log-probability of the emitted token.  With none given: the launch as before.
 void ragged_tail(const at::Tensor& logits, at::Tensor tokens, at::Tensor history,
                  at::Tensor hist_idx, at::Tensor pos, at::Tensor slot, at::Tensor kv_len,
                  at::Tensor active, at::Tensor limit, at::Tensor tick, at::Tensor counter,
                  at::Tensor ctl, at::Tensor fctl, bool sample,
-                 const c10::optional<at::Tensor>& page_table, int64_t n_pages) {
+                 const c10::optional<at::Tensor>& page_table, int64_t n_pages,
+                 const c10::optional<at::Tensor>& row_ctl, const c10::optional<at::Tensor>& row_fctl,
+                 const c10::optional<at::Tensor>& logprob,
+                 const c10::optional<at::Tensor>& hist_logprob) {
   const int dt = check_sample_logits(logits, "ragged_tail");
   const int64_t b = logits.size(0), V = logits.size(1);
   for (const at::Tensor* t : {&tokens, &hist_idx, &pos, &slot, &limit})
@@ -1610,10 +1617,41 @@ void ragged_tail(const at::Tensor& logits, at::Tensor tokens, at::Tensor history
     st.pt_ld = (int)page_table->size(1);
     st.n_pages = (int)n_pages;
   }
+  // per-row form: settings tables (both or neither, sampling only) and the
+  // log-probability outputs (either, both forms of the tail)
+  ema::RaggedRows rr{nullptr, nullptr, nullptr, nullptr, 0};
+  const auto dev = logits.device();
+  TORCH_CHECK(row_ctl.has_value() == row_fctl.has_value(),
+              "ragged_tail: row_ctl and row_fctl come together");
+  if (row_ctl) {
+    TORCH_CHECK(sample, "ragged_tail: row_ctl needs sample = true");
+    TORCH_CHECK(row_ctl->device() == dev && row_ctl->scalar_type() == at::kLong &&
+                    row_ctl->is_contiguous() && row_ctl->dim() == 2 && row_ctl->size(0) == b &&
+                    row_ctl->size(1) == 4 && row_fctl->device() == dev &&
+                    row_fctl->scalar_type() == at::kFloat && row_fctl->is_contiguous() &&
+                    row_fctl->dim() == 2 && row_fctl->size(0) == b && row_fctl->size(1) == 2,
+                "ragged_tail: row_ctl int64 [b, 4], row_fctl float32 [b, 2] on the logits' device");
+    rr.row_ctl = row_ctl->data_ptr<int64_t>();
+    rr.row_fctl = row_fctl->data_ptr<float>();
+  }
+  if (logprob) {
+    TORCH_CHECK(logprob->device() == dev && logprob->scalar_type() == at::kFloat &&
+                    logprob->is_contiguous() && logprob->numel() == b,
+                "ragged_tail: logprob float32 [b] on the logits' device");
+    rr.logprob = logprob->data_ptr<float>();
+  }
+  if (hist_logprob) {
+    TORCH_CHECK(hist_logprob->device() == dev && hist_logprob->scalar_type() == at::kFloat &&
+                    hist_logprob->dim() == 2 && hist_logprob->size(0) == b &&
+                    hist_logprob->size(1) == history.size(1) && hist_logprob->stride(1) == 1,
+                "ragged_tail: hist_logprob float32 [b, H] on the logits' device, H as history's");
+    rr.hist_logprob = hist_logprob->data_ptr<float>();
+    rr.lp_ld = hist_logprob->stride(0);
+  }
   ema::ragged_tail(logits.data_ptr(), logits.stride(0), (int)V, (int)b, dt, sample,
                    tokens.data_ptr<int64_t>(), history.data_ptr<int64_t>(), history.stride(0),
                    history.size(1), st, reinterpret_cast<unsigned*>(counter.data_ptr<int>()),
-                   ctl.data_ptr<int64_t>(), fctl.data_ptr<float>(), cur_stream());
+                   ctl.data_ptr<int64_t>(), fctl.data_ptr<float>(), rr, cur_stream());
 }
 
 // Speculative tail (inference/speculative.py): logits [b * S, V] of a step with
@@ -2083,7 +2121,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("ragged_tail", &ragged_tail, py::arg("logits"), py::arg("tokens"), py::arg("history"),
         py::arg("hist_idx"), py::arg("pos"), py::arg("slot"), py::arg("kv_len"), py::arg("active"),
         py::arg("limit"), py::arg("tick"), py::arg("counter"), py::arg("ctl"), py::arg("fctl"),
-        py::arg("sample") = false, py::arg("page_table") = py::none(), py::arg("n_pages") = 0);
+        py::arg("sample") = false, py::arg("page_table") = py::none(), py::arg("n_pages") = 0,
+        py::arg("row_ctl") = py::none(), py::arg("row_fctl") = py::none(),
+        py::arg("logprob") = py::none(), py::arg("hist_logprob") = py::none());
   m.def("spec_tail", &spec_tail, py::arg("logits"), py::arg("tokens"), py::arg("pos"),
         py::arg("slot"), py::arg("kv_len"), py::arg("history"), py::arg("hist_len"),
         py::arg("limit"), py::arg("active"), py::arg("accepted"), py::arg("tick"), py::arg("ctl"),

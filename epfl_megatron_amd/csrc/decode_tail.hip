@@ -11,7 +11,9 @@
 // sequences: history index, cache slot, key count, position, limit and an
 // active flag per row, so a finished row parks and can be refilled between
 // replays of the same graph.  The selection code (argmax_row, draw_row) is
-// shared; only thread 0's bookkeeping differs.
+// shared; only thread 0's bookkeeping differs.  Its per-row form (template
+// argument X) gives every row its own sampling settings, seed and Philox offset
+// and reports the log-probability of the emitted token.
 // spec_tail_k (inference/speculative.py) is the tail of a speculative greedy
 // step: S logits rows per sequence, one workgroup each, and the last of a
 // sequence's workgroups to arrive verifies the drafts, commits and drafts anew.
@@ -49,15 +51,62 @@ __device__ __forceinline__ void take(float& bv, int& bi, float v, int i) {
   }
 }
 
+// Online log-sum-exp of the raw logits (the ragged tail's log-probability
+// output): sum_i exp(x_i) = s * exp(m), m the running maximum.  m starts at the
+// lowest finite float so that a -inf logit adds exp(-inf) = 0 instead of
+// exp(-inf - -inf); one hardware exp per element, the branch is a select.
+struct Lse {
+  float m, s;
+};
+constexpr float LSE_LOW = -3.4028234664e38f;
+
+__device__ __forceinline__ void lse_add(Lse& a, float x) {
+  const float d = x - a.m, e = __expf(-fabsf(d));
+  a.s = d > 0.f ? a.s * e + 1.f : a.s + e;
+  a.m = fmaxf(a.m, x);
+}
+
+// the rescaling combine of two partial sums
+__device__ __forceinline__ void lse_merge(Lse& a, float om, float os) {
+  const float m = fmaxf(a.m, om);
+  a.s = a.s * __expf(a.m - m) + os * __expf(om - m);
+  a.m = m;
+}
+
+// Merge of the 1024 per-thread pairs in a fixed order (lane butterfly 32, 16,
+// .. 1, then waves 0..15 in sequence on thread 0): same row, same bits.  Ends
+// on a barrier-free read of thread 0's own result; red_m / red_s are 16 floats
+// of LDS each, not in use by anyone else between the two barriers.
+__device__ __forceinline__ void lse_block(Lse& a, float* red_m, float* red_s, int tid) {
+  const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float om = __shfl_xor(a.m, o, 64), os = __shfl_xor(a.s, o, 64);
+    lse_merge(a, om, os);
+  }
+  __syncthreads();
+  if (lane == 0) {
+    red_m[wave] = a.m;
+    red_s[wave] = a.s;
+  }
+  __syncthreads();
+  if (tid == 0) {
+#pragma unroll
+    for (int w = 1; w < 1024 / 64; ++w) lse_merge(a, red_m[w], red_s[w]);
+  }
+}
+
 // argmax of one row over the 1024 threads of a workgroup: the result is valid
-// in thread 0 (shared by greedy_tail_k and the ragged tail)
-template <typename T>
-__device__ __forceinline__ int argmax_row(const T* __restrict__ lr, int V, int tid) {
+// in thread 0 (shared by greedy_tail_k and the ragged tail).  LP: the same
+// sweep carries the log-sum-exp of the row into *lse (thread 0).
+template <typename T, bool LP = false>
+__device__ __forceinline__ int argmax_row(const T* __restrict__ lr, int V, int tid, Lse* lse = nullptr) {
   typedef typename Vec16<T>::t vec;
   constexpr int NV = Vec16<T>::n;
   const int lane = tid & 63, wave = tid >> 6;
   float bv = -INFINITY;
   int bi = 0x7fffffff;
+  Lse acc{LSE_LOW, 0.f};
   // 16-B loads, 8 in flight per thread per round over 1024 threads (one
   // round covers a 32k fp32 vocabulary: the row is latency-, not
   // bandwidth-bound; ld and the row base are 16-B aligned: checked by the
@@ -76,11 +125,19 @@ __device__ __forceinline__ int argmax_row(const T* __restrict__ lr, int V, int t
       const int vi = v0 + u * NT;
       if (vi < nvec) {
 #pragma unroll
-        for (int e = 0; e < NV; ++e) take(bv, bi, elem<T>(x[u], e), vi * NV + e);
+        for (int e = 0; e < NV; ++e) {
+          const float xe = elem<T>(x[u], e);
+          take(bv, bi, xe, vi * NV + e);
+          if constexpr (LP) lse_add(acc, xe);
+        }
       }
     }
   }
-  for (int i = nvec * NV + tid; i < V; i += NT) take(bv, bi, (float)lr[i], i);
+  for (int i = nvec * NV + tid; i < V; i += NT) {
+    const float xe = (float)lr[i];
+    take(bv, bi, xe, i);
+    if constexpr (LP) lse_add(acc, xe);
+  }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float ov = __shfl_xor(bv, o, 64);
@@ -97,6 +154,11 @@ __device__ __forceinline__ int argmax_row(const T* __restrict__ lr, int V, int t
   if (tid == 0) {
 #pragma unroll
     for (int w = 1; w < NT / 64; ++w) take(bv, bi, sv[w], si[w]);
+  }
+  if constexpr (LP) {
+    __shared__ float lm[NT / 64], ls[NT / 64];
+    lse_block(acc, lm, ls, tid);
+    *lse = acc;
   }
   return bi;
 }
@@ -223,11 +285,17 @@ __device__ __forceinline__ void row_for_each(const T* __restrict__ lr, int V, in
 
 // The draw of one row (the filters and the Gumbel-max of the comment above, or
 // the plain argmax at top_k == 1) over the 1024 threads of a workgroup, noise
-// at Philox offset a.offset0 + step: the token is valid in thread 0, before the
-// vocab_limit clamp (shared by sample_tail_k and the ragged tail)
-template <typename T>
-__device__ __forceinline__ int draw_row(const T* __restrict__ lr, int V, int row, int tid,
-                                        const SampleArgs& a, int64_t step) {
+// at Philox counter-high word chi_hi (the row, or 0 for noise that belongs to a
+// request) and offset a.offset0 + step: the token is valid in thread 0, before
+// the vocab_limit clamp (shared by sample_tail_k and the ragged tail).
+// LP: the log-sum-exp of the raw row (before tempering and filtering, all V
+// columns) into *lse, carried through the first sweep each path makes anyway:
+// the argmax sweep (top_k == 1), the draw sweep (no filter), the max sweep
+// (top-p) and the first digit's histogram pass (top-k).  No path reads the row
+// one more time for it.
+template <typename T, bool LP = false>
+__device__ __forceinline__ int draw_row(const T* __restrict__ lr, int V, int chi_hi, int tid,
+                                        const SampleArgs& a, int64_t step, Lse* lse = nullptr) {
   const int lane = tid & 63, wave = tid >> 6;
   __shared__ u64 hist[ST_NB];
   __shared__ u64 swt[ST_NT / 64];
@@ -239,14 +307,18 @@ __device__ __forceinline__ int draw_row(const T* __restrict__ lr, int V, int row
   __shared__ int si[ST_NT / 64];
   float bv = -INFINITY;
   int bi = 0x7fffffff;
+  Lse acc{LSE_LOW, 0.f};
   if (a.top_k == 1) {
-    row_for_each<T>(lr, V, tid, [&](float x, int i) { take(bv, bi, x, i); });
+    row_for_each<T>(lr, V, tid, [&](float x, int i) {
+      take(bv, bi, x, i);
+      if constexpr (LP) lse_add(acc, x);
+    });
   } else {
     const float temp = a.temperature;
     const bool topk = a.top_k > 1, topp = !topk && a.top_p > 0.f;
     uint32_t kstar = 0;
     const uint64_t off = (uint64_t)(a.offset0 + step), seed = (uint64_t)a.seed;
-    const uint64_t chi = (uint64_t)row << 32;
+    const uint64_t chi = (uint64_t)chi_hi << 32;
     auto draw = [&](float y, int i) {
       const U4 r = philox(chi | (uint32_t)(i >> 2), off, seed);
       const int q = i & 3;
@@ -254,7 +326,10 @@ __device__ __forceinline__ int draw_row(const T* __restrict__ lr, int V, int row
       take(bv, bi, y + gumbel(w), i);
     };
     if (!(topk || topp)) {
-      row_for_each<T>(lr, V, tid, [&](float x, int i) { draw(tempered(x, temp), i); });
+      row_for_each<T>(lr, V, tid, [&](float x, int i) {
+        draw(tempered(x, temp), i);
+        if constexpr (LP) lse_add(acc, x);
+      });
     } else {
 #pragma unroll
       for (int j = 0; j < 4; ++j) hist[4 * tid + j] = 0;
@@ -262,7 +337,10 @@ __device__ __forceinline__ int draw_row(const T* __restrict__ lr, int V, int row
       float m = 0.f;
       if (topp) {
         float lm = -INFINITY;
-        row_for_each<T>(lr, V, tid, [&](float x, int) { lm = fmaxf(lm, tempered(x, temp)); });
+        row_for_each<T>(lr, V, tid, [&](float x, int) {
+          lm = fmaxf(lm, tempered(x, temp));
+          if constexpr (LP) lse_add(acc, x);
+        });
         m = block_max(lm, sv);
       }
       __syncthreads();
@@ -289,6 +367,9 @@ __device__ __forceinline__ int draw_row(const T* __restrict__ lr, int V, int row
           row_for_each<T>(lr, V, tid, [&](float x, int) {
             const float y = tempered(x, temp);
             add(y, okey(y));
+            if constexpr (LP) {
+              if (p == 0 && topk) lse_add(acc, x);  // (top-p carried it through the max sweep)
+            }
           });
         }
         __syncthreads();
@@ -384,6 +465,11 @@ __device__ __forceinline__ int draw_row(const T* __restrict__ lr, int V, int row
 #pragma unroll
     for (int w = 1; w < ST_NT / 64; ++w) take(bv, bi, sv[w], si[w]);
   }
+  if constexpr (LP) {
+    __shared__ float lm[ST_NT / 64], ls[ST_NT / 64];
+    lse_block(acc, lm, ls, tid);
+    *lse = acc;
+  }
   return bi;
 }
 
@@ -453,23 +539,55 @@ __global__ __launch_bounds__(1024) void sample_tail_k(const T* __restrict__ logi
 // / KV_PAGE] * KV_PAGE + pos % KV_PAGE, the entry clamped to the pool).  The
 // arrival counter's high bits count the rows still active; the last workgroup
 // advances *tick, writes that count to ctl[5] and re-arms the counter.
-template <typename T, bool SAMPLE>
+//
+// Per-row form, X != 0 (RaggedRows; X = 0 compiles to the tail above, its
+// branches are `if constexpr`):
+//   RAGGED_ROWS  (SAMPLE only) every row takes seed, offset0, top_k and stop_id
+//     from row_ctl[row] and temperature, top_p from row_fctl[row]; vocab_limit
+//     stays ctl[3].  draw_row's branches are uniform over a workgroup, so a
+//     greedy (top_k == 1: no noise, argmax_row's order), a top-k, a top-p and a
+//     temperature-only row sit side by side in one launch.  The noise belongs
+//     to the request, not to its place: Philox counter-high 0, offset offset0 +
+//     hist_idx[row], key seed: the n-th token of a request is the draw of a
+//     one-row lockstep call at (seed, offset0 + n) in whichever row and replay
+//     it is made.  The row parks on its own stop_id.
+//   RAGGED_LOGP  the log-probability of the emitted (clamped) token under the
+//     raw logits row, x[tok] - max - log(sum exp(x - max)) in fp32 over all V
+//     columns, to logprob[row] and hist_logprob[row, hist_idx] (either may be
+//     nullptr).  The (max, sum) pair rides the first sweep of the selection
+//     (argmax_row / draw_row, LP): no path needed an extra sweep of the row;
+//     thread 0 reads x[tok] again, one element.  An inactive row writes nothing.
+constexpr int RAGGED_ROWS = 1, RAGGED_LOGP = 2;
+
+template <typename T, bool SAMPLE, int X>
 __global__ __launch_bounds__(1024) void ragged_tail_k(const T* __restrict__ logits, int64_t ld, int V,
                                                      int64_t* tokens, int64_t* history,
                                                      int64_t hist_ld, int64_t hist_cols,
                                                      RaggedTail st, unsigned* counter, int64_t* ctl,
-                                                     const float* fctl) {
+                                                     const float* fctl, RaggedRows rr) {
+  constexpr bool ROWS = (X & RAGGED_ROWS) != 0, LP = (X & RAGGED_LOGP) != 0;
+  static_assert(SAMPLE || !ROWS, "per-row settings belong to the sampling tail");
   const int row = blockIdx.x, tid = threadIdx.x;
   const bool act = st.active[row] != 0;
-  const int64_t stop_id = ctl[4];
+  int64_t stop_id;
+  if constexpr (ROWS) stop_id = rr.row_ctl[4 * row + 3];
+  else stop_id = ctl[4];
   int bi = 0;
+  Lse lse{0.f, 1.f};
   if (act) {
     const T* lr = logits + (int64_t)row * ld;
-    if constexpr (SAMPLE) {
+    if constexpr (ROWS) {
+      // hist_idx[row]: thread 0 alone stores it, behind draw_row's barriers
+      const int64_t* rc = rr.row_ctl + 4 * row;
+      const SampleArgs a{rc[0], rc[1], rc[2], ctl[3], stop_id, rr.row_fctl[2 * row], rr.row_fctl[2 * row + 1]};
+      bi = draw_row<T, LP>(lr, V, 0, tid, a, st.hist_idx[row], &lse);
+    } else if constexpr (SAMPLE) {
       const SampleArgs a{ctl[0], ctl[1], ctl[2], ctl[3], stop_id, fctl[0], fctl[1]};
-      bi = draw_row<T>(lr, V, row, tid, a, *st.tick);
+      if constexpr (LP) bi = draw_row<T, true>(lr, V, row, tid, a, *st.tick, &lse);
+      else bi = draw_row<T>(lr, V, row, tid, a, *st.tick);
     } else {
-      bi = argmax_row<T>(lr, V, tid);
+      if constexpr (LP) bi = argmax_row<T, true>(lr, V, tid, &lse);
+      else bi = argmax_row<T>(lr, V, tid);
     }
   }
   if (tid != 0) return;
@@ -480,6 +598,13 @@ __global__ __launch_bounds__(1024) void ragged_tail_k(const T* __restrict__ logi
     const int64_t hi = st.hist_idx[row];
     tokens[row] = tok;
     if (hi >= 0 && hi < hist_cols) history[(int64_t)row * hist_ld + hi] = tok;
+    if constexpr (LP) {
+      // (a row of NaNs selects no index: nothing of the row is read then)
+      const float xt = tok >= 0 && tok < V ? (float)logits[(int64_t)row * ld + tok] : NAN;
+      const float lp = (xt - lse.m) - logf(lse.s);
+      if (rr.logprob) rr.logprob[row] = lp;
+      if (rr.hist_logprob && hi >= 0 && hi < hist_cols) rr.hist_logprob[(int64_t)row * rr.lp_ld + hi] = lp;
+    }
     st.hist_idx[row] = hi + 1;
     if ((stop_id >= 0 && tok == stop_id) || hi + 1 >= st.limit[row]) {
       st.active[row] = 0;
@@ -710,15 +835,23 @@ void spec_tail(const void* logits, int64_t ld, int V, int S, int dt, const SpecT
 
 void ragged_tail(const void* logits, int64_t ld, int V, int b, int dt, bool sample, int64_t* tokens,
                  int64_t* history, int64_t hist_ld, int64_t hist_cols, const RaggedTail& st,
-                 unsigned* counter, int64_t* ctl, const float* fctl, hipStream_t s) {
+                 unsigned* counter, int64_t* ctl, const float* fctl, const RaggedRows& rr,
+                 hipStream_t s) {
+  // (row_ctl comes with row_fctl and sample == true: checked by the binding)
+  const bool rows = rr.row_ctl != nullptr, lp = rr.logprob != nullptr || rr.hist_logprob != nullptr;
+#define EMA_RAGGED_TAIL(SAMPLE, X)                                                                 \
+  hipLaunchKernelGGL((ragged_tail_k<T, SAMPLE, X>), dim3((unsigned)b), dim3(1024), 0, s,           \
+                     (const T*)logits, ld, V, tokens, history, hist_ld, hist_cols, st, counter, ctl, \
+                     fctl, rr)
   EMA_DISPATCH_FLOAT(dt, T, {
-    if (sample)
-      hipLaunchKernelGGL((ragged_tail_k<T, true>), dim3((unsigned)b), dim3(1024), 0, s, (const T*)logits,
-                         ld, V, tokens, history, hist_ld, hist_cols, st, counter, ctl, fctl);
-    else
-      hipLaunchKernelGGL((ragged_tail_k<T, false>), dim3((unsigned)b), dim3(1024), 0, s, (const T*)logits,
-                         ld, V, tokens, history, hist_ld, hist_cols, st, counter, ctl, fctl);
+    if (rows && lp) EMA_RAGGED_TAIL(true, RAGGED_ROWS | RAGGED_LOGP);
+    else if (rows) EMA_RAGGED_TAIL(true, RAGGED_ROWS);
+    else if (sample && lp) EMA_RAGGED_TAIL(true, RAGGED_LOGP);
+    else if (sample) EMA_RAGGED_TAIL(true, 0);
+    else if (lp) EMA_RAGGED_TAIL(false, RAGGED_LOGP);
+    else EMA_RAGGED_TAIL(false, 0);
   });
+#undef EMA_RAGGED_TAIL
 }
 
 void greedy_tail(const void* logits, int64_t ld, int V, int b, int dt, int64_t* tokens,

@@ -358,9 +358,25 @@ struct RaggedTail {
   const int* page_table;
   int pt_ld, n_pages;
 };
+// Per-row form of the ragged tail (all nullptr: the tail above).  row_ctl int64
+// [b, 4] = [seed, offset0, top_k, stop_id] and row_fctl float [b, 2] =
+// [temperature, top_p] replace ctl[0..2], ctl[4] and fctl row by row (sample
+// only; vocab_limit stays ctl[3]) and index the noise by the request: Philox
+// counter-high 0, offset offset0 + hist_idx[row].  logprob float [b] /
+// hist_logprob float [b, hist_cols] (row stride lp_ld) receive log_softmax of
+// the raw logits row at the emitted token, the latter where history gets the
+// token; either may be nullptr, and both forms of the tail take them.
+struct RaggedRows {
+  const int64_t* row_ctl;
+  const float* row_fctl;
+  float* logprob;
+  float* hist_logprob;
+  int64_t lp_ld;
+};
 void ragged_tail(const void* logits, int64_t ld, int V, int b, int dt, bool sample, int64_t* tokens,
                  int64_t* history, int64_t hist_ld, int64_t hist_cols, const RaggedTail& st,
-                 unsigned* counter, int64_t* ctl, const float* fctl, hipStream_t s);
+                 unsigned* counter, int64_t* ctl, const float* fctl, const RaggedRows& rr,
+                 hipStream_t s);
 // Tail of one speculative greedy step (inference/speculative.py): b sequences
 // of S rows (2..16), logits [b * S, V]; b * S < 65536.  Semantics at
 // spec_tail_k in decode_tail.hip.  ctl int64 [3] = [stop_id, ngram (0..4), the

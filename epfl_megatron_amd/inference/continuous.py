@@ -121,7 +121,8 @@ class RaggedGreedyDecoder:
 
     sample = False
 
-    def __init__(self, model, inference_params, batch, max_new_tokens, capture=None):
+    def __init__(self, model, inference_params, batch, max_new_tokens, capture=None,
+                 return_log_probs=False):
         if state.model_parallel_is_initialized() and \
                 state.get_pipeline_model_parallel_world_size() > 1:
             raise NotImplementedError("the ragged decode loop needs the whole model (PP = 1)")
@@ -158,6 +159,11 @@ class RaggedGreedyDecoder:
         self.stop_id = -1
         self.ctl[4] = -1
         self.fctl = torch.ones(2, dtype=torch.float32, device=dev)
+        # log_softmax of the raw logits at every emitted token, where history
+        # holds the token (the tail kernel writes both)
+        self.return_log_probs = bool(return_log_probs)
+        self.hist_logprob = z((batch, max_new_tokens), torch.float32) if return_log_probs else None
+        self.row_ctl = self.row_fctl = None  # per-row settings (RaggedSamplingDecoder)
         self._attach()
         self.graph = None
         self.logits = None
@@ -183,10 +189,17 @@ class RaggedGreedyDecoder:
                     and (last.stride(0) * last.element_size()) % 16 == 0):
                 raise RuntimeError("the ragged tail needs bf16 / fp16 / fp32 logits on the GPU "
                                    "with 16-byte aligned rows")
+            page_table, n_pages = self._table() or (None, 0)
             ext().ragged_tail(last, *self._state(), self.tail_counter, self.ctl, self.fctl,
-                              self.sample, *self._table())
+                              self.sample, page_table, n_pages, row_ctl=self.row_ctl,
+                              row_fctl=self.row_fctl, hist_logprob=self.hist_logprob)
         else:
-            ragged_tail_reference(self._select(last), *self._state(), self.ctl, *self._table())
+            tok = self._select(last)
+            if self.return_log_probs:
+                rows = (self.active != 0).nonzero().flatten()
+                lp = torch.log_softmax(last.float(), -1).gather(1, tok.view(-1, 1)).view(-1)
+                self.hist_logprob[rows, self.hist_idx[rows]] = lp[rows]
+            ragged_tail_reference(tok, *self._state(), self.ctl, *self._table())
         return logits
 
     def _select(self, last):
@@ -317,6 +330,17 @@ class RaggedSamplingDecoder(RaggedGreedyDecoder):
     t``, whatever a row's history index is: a refilled row does not replay
     its predecessor's noise.
 
+    ``per_row=True`` (fixed at construction: a captured graph keeps its
+    kernel) runs the per-row form of the tail instead: ``prime(...,
+    sampling=dict(top_k=, top_p=, temperature=, seed=, offset=))`` gives a row
+    its own settings (``configure``'s where left out), so a greedy request
+    sits beside a top-p one, and its own noise: token ``n`` of the row draws
+    at Philox ``(seed, offset + n)`` with counter row 0, the draw of a one-row
+    ``sample_fused`` call, whichever row and replay it falls in.  A row
+    primed without a seed takes ``max_new`` fresh offsets from the generator.
+    ``return_log_probs=True`` (both ragged decoders): ``hist_logprob`` holds
+    ``log_softmax`` of the raw logits at every token of ``history``.
+
     Offsets are reserved from the CUDA generator (TP rank 0's under tensor
     parallelism) in blocks of ``RESERVE`` replays, and the generator is
     advanced past a block at the moment the block is taken: the first one by
@@ -331,9 +355,23 @@ class RaggedSamplingDecoder(RaggedGreedyDecoder):
     RESERVE = 1024
 
     def __init__(self, model, inference_params, batch, max_new_tokens, vocab_size=None,
-                 capture=None):
-        super().__init__(model, inference_params, batch, max_new_tokens, capture)
+                 capture=None, per_row=False, return_log_probs=False):
+        super().__init__(model, inference_params, batch, max_new_tokens, capture, return_log_probs)
         self.vocab_size = vocab_size
+        # per_row: the per-row form of the tail, fixed at construction (a
+        # captured graph keeps its kernel).  row_ctl [b, 4] = [seed, offset0,
+        # top_k, stop_id], row_fctl [b, 2] = [temperature, top_p]: written by
+        # prime, read by the kernel.  Token n of a row draws its noise at
+        # (seed, offset0 + n), Philox counter-high 0: the draw of a one-row
+        # sample_fused call, wherever the request sits.
+        self.per_row = bool(per_row)
+        if per_row:
+            dev = self.tokens.device
+            self.row_ctl = torch.zeros(batch, 4, dtype=torch.long, device=dev)
+            self.row_ctl[:, 3] = -1
+            self.row_fctl = torch.ones(batch, 2, dtype=torch.float32, device=dev)
+            self.row_fctl[:, 1] = 0.0
+        self.row_settings = [None] * batch  # host copy: (settings, seed, offset0) per row
         self.seed = self.offset0 = None
         self.ticks = 0          # replays so far (= the device tick)
         self.block_end = 0      # one past the last offset of the reserved block
@@ -359,6 +397,9 @@ class RaggedSamplingDecoder(RaggedGreedyDecoder):
         return broadcast_seed_offset(seed, off, dev)
 
     def _new_block(self):
+        if self.per_row:  # no shared noise index: every row carries its own
+            self.seed, self.offset0, self.block_end = 0, 0, float("inf")
+            return
         self.seed, off = self._take(self.RESERVE)
         self.offset0 = off - self.ticks  # offset0 + tick continues at `off`
         self.block_end = off + (self.RESERVE + 3) // 4 * 4
@@ -375,14 +416,10 @@ class RaggedSamplingDecoder(RaggedGreedyDecoder):
         return seed, off
 
     def configure(self, top_k=0, top_p=0.0, temperature=1.0, stop_id=-1):
-        """The sampling settings and the stop token of every row from now on;
-        the first call reserves the first block of Philox offsets."""
-        if top_k < 0 or (top_k > 0 and top_p != 0.0):
-            raise AssertionError("cannot set both top-k and top-p samplings")
-        if not 0.0 <= top_p <= 1.0:
-            raise AssertionError("top-p should be in (0, 1]")
-        if not temperature > 0.0:
-            raise AssertionError("temperature should be positive")
+        """The sampling settings and the stop token of every row from now on
+        (``per_row``: of every row primed without settings of its own); the
+        first call reserves the first block of Philox offsets."""
+        self._check_settings(top_k, top_p, temperature)
         if self.seed is None:
             self._new_block()
         self.settings = dict(top_k=top_k, top_p=top_p, temperature=temperature)
@@ -398,13 +435,75 @@ class RaggedSamplingDecoder(RaggedGreedyDecoder):
             self._new_block()
         self.ticks += 1
 
-    def prime(self, row, first_token, position, max_new, pages=None):
+    @staticmethod
+    def _check_settings(top_k, top_p, temperature):
+        if top_k < 0 or (top_k > 0 and top_p != 0.0):
+            raise AssertionError("cannot set both top-k and top-p samplings")
+        if not 0.0 <= top_p <= 1.0:
+            raise AssertionError("top-p should be in (0, 1]")
+        if not temperature > 0.0:
+            raise AssertionError("temperature should be positive")
+
+    def set_stop_id(self, stop_id):
+        super().set_stop_id(stop_id)
+        if self.per_row:
+            with torch.no_grad():
+                self.row_ctl[:, 3] = self.stop_id
+
+    def resolve(self, sampling, n_offsets):
+        """``sampling`` (None or a dict of ``top_k`` / ``top_p`` / ``temperature``
+        / ``seed`` / ``offset``; a missing or None setting takes ``configure``'s)
+        as (settings, seed, offset0), validated as ``configure`` validates.
+        Without a seed, ``n_offsets`` offsets are taken from the generator, so
+        no two requests share noise."""
+        sampling = dict(sampling or {})
+        seed, off = sampling.pop("seed", None), sampling.pop("offset", None)
+        unknown = set(sampling) - set(self.settings)
+        if unknown:
+            raise ValueError(f"unknown sampling settings {sorted(unknown)}")
+        s = dict(self.settings, **{k: v for k, v in sampling.items() if v is not None})
+        if sampling.get("top_k") and sampling.get("top_p") is None:
+            s["top_p"] = 0.0  # the request's filter replaces the default's
+        elif sampling.get("top_p") and sampling.get("top_k") is None:
+            s["top_k"] = 0
+        self._check_settings(**s)
+        if seed is None:
+            if off is not None:
+                raise ValueError("an offset needs its seed")
+            seed, off = self._take(n_offsets)
+        return s, int(seed) & (2 ** 63 - 1), int(off or 0)
+
+    def prime(self, row, first_token, position, max_new, pages=None, sampling=None):
+        """``sampling``: this row's own settings, seed and first Philox offset
+        (see ``resolve``), ``per_row`` decoders only: small copies into the
+        row's table entries, the captured graph is untouched."""
         if self.seed is None:
             self.configure()
+        if sampling is not None and not self.per_row:
+            raise ValueError("per-row sampling settings need RaggedSamplingDecoder(per_row=True)")
+        if self.per_row:
+            s, seed, off = self.resolve(sampling, max_new)
         super().prime(row, first_token, position, max_new, pages)
+        if self.per_row:
+            self.row_settings[row] = (s, seed, off)
+            with torch.no_grad():
+                self.row_ctl[row] = torch.tensor([seed, off, s["top_k"], self.stop_id],
+                                                 dtype=torch.long).to(self.row_ctl.device)
+                self.row_fctl[row] = torch.tensor([s["temperature"], s["top_p"]],
+                                                  dtype=torch.float32).to(self.row_fctl.device)
 
     def _select(self, last):
         from ..ops.sampling import sample_ref
+        if self.per_row:  # the kernel's indexing: counter row 0, offset0 + hist_idx
+            tok = last.argmax(-1)
+            for row in (self.active != 0).nonzero().flatten().tolist():
+                s, seed, off = self.row_settings[row]
+                if s["top_k"] != 1:
+                    tok[row] = sample_ref(last[row:row + 1].float().cpu(), seed,
+                                          off + int(self.hist_idx[row]), **s)[0]
+            if self.vocab_size:
+                tok = tok.clamp(max=self.vocab_size - 1)
+            return tok
         s = self.settings
         if s["top_k"] == 1:
             tok = last.argmax(-1)
@@ -478,6 +577,8 @@ class ContinuousBatcher:
         self.dec = decoder
         self.queue = deque()
         self.requests = []      # (prompt, max_new) by request id
+        self.sampling = []      # the request's own sampling settings, by request id
+        self.log_probs = {}     # request id -> log-probabilities (return_log_probs decoders)
         self.results = {}
         self.rows = [None] * batch  # request id, first token per busy row
         self.primed = []        # (row, position, max_new) of every prime, for inspection
@@ -497,8 +598,20 @@ class ContinuousBatcher:
         self.prefilled_tokens = 0
         self.evictions = 0
 
-    def submit(self, prompt_tokens, max_new_tokens):
-        """Queue a request; returns its id (= its index in ``run()``'s result)."""
+    def submit(self, prompt_tokens, max_new_tokens, top_k=None, top_p=None, temperature=None,
+               seed=None):
+        """Queue a request; returns its id (= its index in ``run()``'s result).
+        ``top_k`` / ``top_p`` / ``temperature`` / ``seed``: the request's own
+        sampling settings (a ``RaggedSamplingDecoder(per_row=True)``; None: the
+        decoder's ``configure``).  With a ``seed`` the request's tokens depend
+        on (prompt, settings, seed) alone: token n draws at Philox (seed, n),
+        the first one, from the prefill logits, included."""
+        sampling = dict(top_k=top_k, top_p=top_p, temperature=temperature, seed=seed)
+        if any(v is not None for v in sampling.values()):
+            if not getattr(self.dec, "per_row", False):
+                raise ValueError("per-request sampling settings need a "
+                                 "RaggedSamplingDecoder(per_row=True)")
+            self.dec.resolve(dict(sampling, seed=0), 0)  # refuse bad settings here, not at admission
         prompt = torch.as_tensor(prompt_tokens, dtype=torch.long).view(-1)
         if prompt.numel() < 2:
             raise ValueError("a prompt needs at least two tokens (a one-token prefill would take "
@@ -514,6 +627,7 @@ class ContinuousBatcher:
                                  f"{self.pool.n_pages - 1} usable pages or the "
                                  f"{self.ip.page_table.shape[1]} pages of a row")
         self.requests.append((prompt, int(max_new_tokens)))
+        self.sampling.append(sampling)
         self.queue.append(len(self.requests) - 1)
         return len(self.requests) - 1
 
@@ -540,7 +654,8 @@ class ContinuousBatcher:
         before it are in the row's shared pages) into cache column ``row``, in
         the pieces of ``_pieces``; the device slot tensors are hidden so that
         no layer takes the graph branch, and the host offsets are restored for
-        the decode step (whose graph branch reads neither)."""
+        the decode step (whose graph branch reads neither).  Returns the logits
+        of the last position, ``[1, V]``."""
         ip, dev = self.ip, self.dec.tokens.device
         saved = (ip.device_offset, ip.device_kv_len, ip.sequence_len_offset, ip.batch_size_offset,
                  ip.continue_prefill)
@@ -556,17 +671,33 @@ class ContinuousBatcher:
                 with torch.no_grad():
                     logits = self.model(tokens[:, a:b], pos, None, inference_params=ip)
             self.prefilled_tokens += n - s0
-            return self._first(logits[:, -1])
+            return logits[:, -1]
         finally:
             (ip.device_offset, ip.device_kv_len, ip.sequence_len_offset, ip.batch_size_offset,
              ip.continue_prefill) = saved
 
-    def _first(self, last):
-        if self.dec.sample and self.dec.settings["top_k"] != 1:
+    def _first(self, last, rid):
+        """Request ``rid``'s first token from its prefill logits ``last [1, V]``
+        (a ``return_log_probs`` decoder: its log-probability goes to
+        ``log_probs``), and what ``prime`` takes as ``sampling``.  Per-row
+        decoders: drawn at the request's (seed, offset0 + 0), a one-row call, so
+        Philox counter row 0 as in the tail; the decoder goes on at offset0 + 1."""
+        dec, sampling = self.dec, None
+        if getattr(dec, "per_row", False):
             from ..ops.sampling import sample_fused
-            return int(sample_fused(last, vocab_size=self.dec.vocab_size,
-                                    seed_offset=self.dec.draw_seed_offset(), **self.dec.settings))
-        return int(last.argmax(-1))
+            s, seed, off = dec.resolve(self.sampling[rid], self.requests[rid][1])
+            sampling = dict(s, seed=seed, offset=off + 1)
+            tok = int(last.argmax(-1)) if s["top_k"] == 1 else \
+                int(sample_fused(last, vocab_size=dec.vocab_size, seed_offset=(seed, off), **s))
+        elif dec.sample and dec.settings["top_k"] != 1:
+            from ..ops.sampling import sample_fused
+            tok = int(sample_fused(last, vocab_size=dec.vocab_size,
+                                   seed_offset=dec.draw_seed_offset(), **dec.settings))
+        else:
+            tok = int(last.argmax(-1))
+        if dec.return_log_probs:
+            self.log_probs[rid] = [float(torch.log_softmax(last.float(), -1)[0, tok])]
+        return tok, sampling
 
     def _admit(self, row):
         """Fill ``row`` from the queue until a request needs the decoder.
@@ -596,7 +727,7 @@ class ContinuousBatcher:
                 # the table row before the eager prefill, which scatters by it
                 self.dec.write_table(row, table, prompt.numel() + max_new)
             self.queue.popleft()
-            first = self._prefill(row, prompt, len(chain) * KV_PAGE)
+            first, sampling = self._first(self._prefill(row, prompt, len(chain) * KV_PAGE), rid)
             if self.cache is not None:
                 self.prefix_log.append((rid, len(chain)))
                 self.prefix_hit_pages += len(chain)
@@ -609,7 +740,8 @@ class ContinuousBatcher:
                 if self.paged:
                     self._give_back(row, pages, chain)
                 continue
-            self.dec.prime(row, first, prompt.numel(), max_new - 1)
+            self.dec.prime(row, first, prompt.numel(), max_new - 1,
+                           **({} if sampling is None else dict(sampling=sampling)))
             self.primed.append((row, prompt.numel(), max_new - 1))
             self.rows[row] = (rid, first)
             self.row_pages[row] = pages
@@ -630,6 +762,8 @@ class ContinuousBatcher:
     def _collect(self, row, hist_idx):
         rid, first = self.rows[row]
         self.results[rid] = [first] + self.dec.history[row, :hist_idx[row]].tolist()
+        if self.dec.return_log_probs:
+            self.log_probs[rid] += self.dec.hist_logprob[row, :hist_idx[row]].tolist()
         if self.paged:
             self._give_back(row, self.row_pages[row], self.row_cached[row] or ())
             self.row_pages[row] = self.row_cached[row] = None
@@ -637,7 +771,9 @@ class ContinuousBatcher:
         self.rows[row] = None
 
     def run(self):
-        """Serve every queued request; token lists in submission order."""
+        """Serve every queued request; token lists in submission order (a
+        ``return_log_probs`` decoder: ``log_probs[id]`` holds, token for token,
+        ``log_softmax`` of the raw logits at the request's tokens)."""
         dec = self.dec
         for row in range(self.batch):
             if self.rows[row] is None:

@@ -20,6 +20,12 @@ Semantics (fixed so that ``sample_ref`` reproduces the kernel token for token):
 4. ``top_k == 1`` is the plain argmax (first maximum, no noise).
 5. The token is clamped to ``vocab_size - 1``.
 
+Request-indexed noise (the per-row ragged tail, ``inference/continuous.py``):
+a request with ``(seed, offset0)`` draws its token ``n`` with ``row = 0`` and
+``offset = offset0 + n`` whichever batch row it sits in, i.e. exactly
+``sample_fused`` / ``sample_ref`` on that one logits row with ``seed_offset =
+(seed, offset0 + n)``; the CPU decoders call ``sample_ref`` that way.
+
 ``sample_fused`` is the public entry (one launch on the GPU, ``sample_ref`` on
 CPU tensors); ``sample_ref`` is the fp64 NumPy transcription: the CPU path and
 the oracle of the GPU tests.

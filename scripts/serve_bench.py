@@ -36,6 +36,12 @@ when nothing matches).  Reports useful tokens/s and the mean time from a
 request's admission to its first token.  The baseline is the paged batcher
 without the cache.
 
+--continuous --mixed_sampling [--log_probs]: the request list with one sampling
+setting for all (the shared-setting tail) and with four settings cycling over
+the requests, each with its own seed (RaggedSamplingDecoder(per_row=True);
+--log_probs: return_log_probs too), alternating in one process; reports useful
+tokens/s of both and the tail kernel's time per launch in each form.
+
 --ragged_cost: what per-row state costs a uniform batch: RaggedGreedyDecoder
 against GraphedGreedyDecoder from the same prefilled cache, --reps repetitions
 each, alternating; the spread of the lockstep decoder's repetitions is the margin.
@@ -64,6 +70,7 @@ Usage: python scripts/serve_bench.py [--batches 1,8,32] [--graph [--speculative 
        [--paged_cost [--reps 3] [--kv_pages N]]
        [--continuous --prefix_share [--system_prompt 1024] [--prompt_range LO,HI]
         [--no_prefix_range LO,HI] [--prefill_chunk C] [--reps 3]]
+       [--continuous --mixed_sampling [--log_probs] [--reps 3]]
 """
 import argparse
 import json
@@ -121,6 +128,11 @@ def main():
     ap.add_argument("--prefix_share", action="store_true",
                     help="--continuous: the paged batcher with and without prefix_cache on a "
                          "request list with a common system prompt, and on one without")
+    ap.add_argument("--mixed_sampling", action="store_true",
+                    help="--continuous: four sampling settings cycling over the requests (per-row "
+                         "tail) against one setting for all, tokens/s of both")
+    ap.add_argument("--log_probs", action="store_true",
+                    help="--mixed_sampling: with the log-probability outputs")
     ap.add_argument("--system_prompt", type=int, default=1024,
                     help="--prefix_share: tokens of the common prefix")
     ap.add_argument("--no_prefix_range", default="16,1920",
@@ -196,6 +208,8 @@ def main():
         return paged_cost(a, m)
     if a.continuous and a.prefix_share:
         return prefix_share(a, m)
+    if a.continuous and a.mixed_sampling:
+        return mixed_sampling(a, m)
     if a.continuous:
         return continuous(a, m, sampling, skw)
     if a.ragged_cost:
@@ -372,6 +386,85 @@ def continuous(a, m, sampling, skw):
                          static_replays=steps)
         for r in res[-len(a.poll_every.split(",")):]:
             print(json.dumps(r), flush=True)
+    return res
+
+
+MIXED = (dict(top_k=1), dict(top_k=50), dict(top_p=0.9, temperature=0.8), dict(temperature=1.2))
+
+
+def _tail_us(B, mixed, log_probs, reps=200):
+    """Microseconds per launch of the ragged sampling tail alone on random
+    bf16 logits [B, 32000], every row active: the shared-setting form (top-p 0.9
+    at T 0.8) or the per-row form with the settings of MIXED cycling."""
+    import torch
+    from epfl_megatron_amd.ops._ext import ext
+    dev, L = "cuda", torch.long
+    logits = (torch.randn(B, 32000, device=dev) * 3).bfloat16()
+
+    def z(*shape, dtype=L):
+        return torch.zeros(*shape, dtype=dtype, device=dev)
+    state = (z(B), z(B, 8), z(B), z(B), z(B), z(B, dtype=torch.int32),
+             torch.ones(B, dtype=torch.int32, device=dev), torch.full((B,), 1 << 40, device=dev), z(1))
+    ctl = torch.tensor([1, 0, 0, 32000, -1, 0], device=dev)
+    fctl = torch.tensor([0.8, 0.9], device=dev)
+    kw = {}
+    if mixed:
+        s = [dict(dict(top_k=0, top_p=0.0, temperature=1.0), **MIXED[i % 4]) for i in range(B)]
+        kw.update(row_ctl=torch.tensor([[i, 0, x["top_k"], -1] for i, x in enumerate(s)], device=dev),
+                  row_fctl=torch.tensor([[x["temperature"], x["top_p"]] for x in s], device=dev))
+    if log_probs:
+        kw.update(hist_logprob=z(B, 8, dtype=torch.float32))
+    counter = z(1, dtype=torch.int32)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    for i in range(reps + 20):
+        if i == 20:
+            ev[0].record()
+        ext().ragged_tail(logits, *state, counter, ctl, fctl, True, **kw)
+    ev[1].record()
+    torch.cuda.synchronize()
+    return round(1e3 * ev[0].elapsed_time(ev[1]) / reps, 2)
+
+
+def mixed_sampling(a, m):
+    """--continuous --mixed_sampling [--log_probs]: the seeded request list
+    through ContinuousBatcher with one setting for all (top-p 0.9 at T 0.8, the
+    shared-setting tail) and with the four settings of MIXED cycling over the
+    requests (the per-row tail; --log_probs: with the log-probability outputs),
+    alternating in one process, and the tail kernel's time per launch."""
+    import torch
+    from epfl_megatron_amd.inference import ContinuousBatcher, RaggedSamplingDecoder
+    from epfl_megatron_amd.inference.forward_step import InferenceParams
+    (plo, phi), (glo, ghi) = ([int(x) for x in r.split(",")] for r in (a.prompt_range, a.gen_range))
+    cap, poll = max(phi + ghi, a.capacity), int(a.poll_every.split(",")[0])
+    res = []
+    for B in [int(x) for x in a.batches.split(",")]:
+        n = a.requests or 4 * B
+        g = torch.Generator().manual_seed(a.seed)
+        plens = torch.randint(plo, phi + 1, (n,), generator=g).tolist()
+        gens = torch.randint(glo, ghi + 1, (n,), generator=g).tolist()
+        prompts = [torch.randint(0, 32000, (p,), generator=g) for p in plens]
+        cbs = {}
+        for mixed in (False, True):
+            ip = InferenceParams(B, cap)
+            dec = RaggedSamplingDecoder(m, ip, B, ghi, vocab_size=32000, per_row=mixed,
+                                        return_log_probs=mixed and a.log_probs)
+            dec.configure(**({} if mixed else dict(top_p=0.9, temperature=0.8)))
+            cbs[mixed] = ContinuousBatcher(m, ip, B, cap, poll_every=poll, decoder=dec)
+        tps = {False: [], True: []}
+        for rep in range(a.reps + 1):  # rep 0 warms up: the capture, the allocator, the prefills
+            for mixed, cb in cbs.items():
+                for i, (p, gn) in enumerate(zip(prompts, gens)):
+                    cb.submit(p, gn, **(dict(MIXED[i % 4], seed=a.seed + i) if mixed else {}))
+                out, dt = _timed(cb.run)
+                assert [len(o) for o in out[-n:]] == gens and cb.dec.captures == 1
+                if rep:
+                    tps[mixed].append(round(sum(gens) / dt, 1))
+        r = {"mode": "mixed_sampling", "batch": B, "requests": n, "log_probs": bool(a.log_probs),
+             "uniform_tokens_per_s": tps[False], "mixed_tokens_per_s": tps[True],
+             "uniform_tail_us": _tail_us(B, False, False),
+             "mixed_tail_us": _tail_us(B, True, a.log_probs)}
+        print(json.dumps(r), flush=True)
+        res.append(r)
     return res
 
 
